@@ -14,7 +14,15 @@ Workloads (synthetic scenes, slamgpu/scene.py; fp64 arithmetic, the reference's 
   --config C5: BASELINE config 5 — 200 keyframes / ~194k landmarks / ~1.95M observations (seed 5),
       SolveFrames(map, 198, 200, 2.0); N > 1: strong scaling, the same problem's landmarks sharded over the
       ranks; value = K / time.
-The default run also measures the other workload (C5 next to a C2 headline: strong over the same N ranks).
+A plain run (`--gpus N --steps K --warmup W`) does what the headline figure needs and no more: it builds the
+workload, warms up, times the K steps, writes the outputs if `--dump-outputs DIR` is given, and prints the line;
+the fields of the other measurements are null in it.  `--full` adds everything described below: the per-kernel
+and `lm_regime` passes, `solve_from_start`, the other workload (C5 next to a C2 headline: strong over the same N
+ranks), the scaled sweep, SolveAllFrames, the scaling model, the CPU baselines and the front end.
+
+`--dump-outputs DIR` writes what the K-th timed iteration left, as a caller of the solver receives it
+(sg_ba_download): DIR/q.npy (frames x 4), t.npy (frames x 3), X.npy (landmarks x 4) and cost.npy, float64 (and
+k.npy when the intrinsics are free).  The scene generator is seeded, so the inputs are the same from run to run.
 
 The timed region is K LM iterations with termination disabled after W warm-up iterations, and every
 iteration is SURVEY.md 8d's full unit of work: linearize + Schur + Cholesky + back-substitution + candidate
@@ -53,6 +61,14 @@ def parse():
     ap.add_argument("--points", type=int, default=20000, help="landmarks of the config-2 scene")
     ap.add_argument("--frames", type=int, default=50)
     ap.add_argument("--config", choices=("C2", "C5"), default="C2", help="headline workload")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, measure everything else: the per-kernel and Ceres-regime "
+                         "passes, solves from the start, the other workload, the scaled sweep, SolveAllFrames, the "
+                         "scaling model, the CPU baselines and the front end (each has its own switch below); "
+                         "--only implies it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left (poses q, t, landmarks X, the cost) "
+                         "as DIR/<name>.npy (float64)")
     ap.add_argument("--other", type=int, default=1, help="also measure the other BA workload (C5 / C2)")
     ap.add_argument("--cpu-runs", type=int, default=7, help="CPU-baseline timed runs per leg (0: skip)")
     ap.add_argument("--cpu-seconds", type=float, default=4.0, help="front-end CPU-baseline sample (0: skip)")
@@ -74,6 +90,14 @@ def parse():
     ap.add_argument("--only", choices=("all", "C2", "C5", "sweep", "frontend"), default="all",
                     help="profiling runs: one workload alone (its kernels are then the only ones launched)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.only != "all":
+        args.full = True
+    if not args.full:   # a plain run: set up, warm up, time the K steps, print the line
+        args.other = args.cpu_runs = args.sweep_obs = args.frontend = args.solve_all = 0
+        args.model_scaling = args.weak = 0
+        args.cpu_seconds = 0.0
     if args.only != "all":
         args.solve_all = 0
         args.cpu_runs = 0
@@ -464,13 +488,29 @@ class Runner:
         assert s1["sync_timeouts"] == 0 and s1["num_lm_iterations"] == warmup + steps, s1
         return elapsed, s0, s1
 
-    def timed(self, steps, warmup):
+    def timed(self, steps, warmup, full=True, dump=False):
         """W warm-up then exactly K LM iterations (termination disabled, every iteration linearizes: the
-        SURVEY.md 8d unit), barrier + synchronize on both sides, max over ranks; then the same K with
-        per-kernel HIP-event timing; then the same K in Ceres's regime (no linearization after a rejected
-        step), reported beside the headline."""
+        SURVEY.md 8d unit), barrier + synchronize on both sides, max over ranks; with `dump`, the state the
+        K-th iteration left is then downloaded as a caller of the solver would receive it.  With `full`: then
+        the same K with per-kernel HIP-event timing; then the same K in Ceres's regime (no linearization after
+        a rejected step), reported beside the headline."""
         g = self.solver
         elapsed, s0, s1 = self._timed_block(steps, warmup, 1)
+        outputs = None
+        if dump:
+            p = self.prob
+            start = [a.copy() for a in (p.q, p.t, p.X, p.k)]
+            g.download()   # into the arrays the solver was loaded from
+            outputs = {"q": p.q.reshape(-1, 4).copy(), "t": p.t.reshape(-1, 3).copy(),
+                       "X": p.X.reshape(-1, 4).copy(), "cost": np.array([s1["final_cost"]])}
+            if p.cameras_free:
+                outputs["k"] = p.k.reshape(-1, 7).copy()
+            for a, b in zip((p.q, p.t, p.X, p.k), start):   # the later measurements start from the same problem
+                a[:] = b
+        head = {"elapsed": elapsed, "accepted": s1["num_successful_steps"] - s0["num_successful_steps"],
+                "summary": s1, "outputs": outputs}
+        if not full:
+            return {**head, "kt": None, "work": None, "lin_active": None, "lm_regime": None}
         g.set_timing(True)
         g.iterate(steps)
         g.sync()
@@ -482,9 +522,8 @@ class Runner:
               "accepted_frac": (l1["num_successful_steps"] - l0["num_successful_steps"]) / steps,
               "note": "Ceres regime: a rejected step skips the linearization, so this figure depends on how many "
                       "of the K steps after W warm-up steps are rejected"}
-        return {"elapsed": elapsed, "accepted": s1["num_successful_steps"] - s0["num_successful_steps"],
-                "kt": kt, "work": g.kernel_work(), "lin_active": s2["num_lm_iterations"] - s1["num_lm_iterations"],
-                "summary": s1, "lm_regime": lm}
+        return {**head, "kt": kt, "work": g.kernel_work(),
+                "lin_active": s2["num_lm_iterations"] - s1["num_lm_iterations"], "lm_regime": lm}
 
     def solve_from_start(self):
         """Complete solves from the perturbed start (termination on): iterations over wall time (includes
@@ -583,12 +622,12 @@ def kernel_report(res, steps, n_text, workload):
     return {k: round(v, 5) for k, v in per_iter_ms.items()}, roof, sweep
 
 
-def run_workload(cfg, args, n_gpus, rank, local, dist, steps, warmup, weak=False):
+def run_workload(cfg, args, n_gpus, rank, local, dist, steps, warmup, weak=False, dump=False):
     full, prob, desc = make_workload(cfg, n_gpus, rank, args.points, args.frames, weak)
     r = Runner(prob, local, rank, n_gpus, dist, args.comm)
-    res = r.timed(steps, warmup)
+    res = r.timed(steps, warmup, args.full, dump)
     info = r.solver.info()
-    start = r.solve_from_start()
+    start = r.solve_from_start() if args.full else None
     # shard balance: every rank's observations / pairs, gathered
     bal = None
     if dist is not None:
@@ -764,6 +803,24 @@ def model_scaling(local, full, full_kernel_ms, ns=(2, 4, 8), steps=20, warmup=3,
     return out
 
 
+DUMP_BUDGET = 64e6   # bytes of --dump-outputs files in all
+
+
+def write_outputs(out_dir, outputs, rank, n_gpus):
+    """--dump-outputs: every array as out_dir/<name>.npy (float64; a rank of N > 1 writes its own shard as
+    <name>_rank<r>.npy).  Arrays are written whole while they fit DUMP_BUDGET together; beyond it, each array
+    over its share is cut to a fixed seeded sample of its rows (in row order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET / n_gpus / max(len(outputs), 1)
+    whole = sum(a.nbytes for a in outputs.values()) * n_gpus <= DUMP_BUDGET
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if not whole and a.nbytes > share:
+            keep = max(1, int(share // (a.nbytes // len(a))))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ("_rank%d" % rank if n_gpus > 1 else "") + ".npy"), a)
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -825,7 +882,10 @@ def main():
     TRAFFIC_APPLIES = n_gpus == 1
 
     full, prob, desc, res, info, start, bal = run_workload(args.config, args, n_gpus, rank, local, dist,
-                                                           args.steps, args.warmup)
+                                                           args.steps, args.warmup,
+                                                           dump=args.dump_outputs is not None)
+    if args.dump_outputs is not None:
+        write_outputs(args.dump_outputs, res["outputs"], rank, n_gpus)
     other = None
     if args.other:
         ocfg = "C2" if c5 else "C5"
@@ -863,7 +923,7 @@ def main():
         return
 
     per_iter_ms, roof, sweep = kernel_report(res, args.steps, "n=%d, band %d tiles" % (info["n"], info["band_tiles"]),
-                                             args.config)
+                                             args.config) if args.full else (None, None, None)
     scal1 = model_scaling(local, full, per_iter_ms) if n_gpus == 1 and args.model_scaling else None
 
     sweep_scaled = bench_sweep(local, args.sweep_obs) if args.sweep_obs > 0 and n_gpus == 1 else None
@@ -915,7 +975,7 @@ def main():
         "cpu_baseline": cpu,
         "speedup_vs_cpu": (value / cpu["value"]) if cpu and cpu["value"] else None,
         "speedup_vs_cpu_from_start": (start["iters_per_s_wall"] / cpu["value"])
-        if cpu and cpu["value"] and start["iters_per_s_wall"] else None,
+        if cpu and cpu["value"] and start and start["iters_per_s_wall"] else None,
         "lm_state": {"final_cost": res["summary"]["final_cost"], "radius": res["summary"]["trust_region_radius"]},
         "shard_balance": bal,
         "strong_scaling_model": scal1,

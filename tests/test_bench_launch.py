@@ -28,3 +28,27 @@ def test_rccl_needs_one_gpu_per_rank():
     r = _run(["--gpus", "64", "--comm", "rccl"], WORLD_SIZE="64", RANK="0", LOCAL_RANK="0")
     assert r.returncode != 0 and "one GPU per rank" in r.stderr
     assert r.stdout.strip() == ""
+
+
+def _parse(monkeypatch, argv):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    return bench.parse()
+
+
+EXTRAS = ("other", "cpu_runs", "cpu_seconds", "sweep_obs", "frontend", "solve_all", "model_scaling", "weak")
+
+
+def test_plain_run_measures_the_headline_alone(monkeypatch):
+    a = _parse(monkeypatch, ["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not a.full and a.steps == 7 and a.warmup == 3 and a.dump_outputs is None
+    assert all(not getattr(a, k) for k in EXTRAS)
+
+
+def test_full_keeps_every_measurement_and_its_switch(monkeypatch):
+    a = _parse(monkeypatch, ["--gpus", "1", "--steps", "7", "--warmup", "3", "--full"])
+    assert a.full and all(getattr(a, k) for k in EXTRAS)
+    a = _parse(monkeypatch, ["--full", "--frontend", "0", "--dump-outputs", "d"])
+    assert a.full and a.frontend == 0 and a.other == 1 and a.dump_outputs == "d"
+    a = _parse(monkeypatch, ["--only", "sweep"])   # a profiling run of one of --full's workloads
+    assert a.full and a.sweep_obs > 0 and not a.other and not a.frontend

@@ -137,7 +137,7 @@ def test_bench_two_ranks_host_transport(launch):
     is the largest per-iteration entry (it did not: KeyError 'exchange')."""
     import json
     import subprocess
-    args = [os.path.join(ROOT, "bench.py"),
+    args = [os.path.join(ROOT, "bench.py"), "--full",   # the per-kernel report is part of --full
             "--gpus", "2", "--steps", "5", "--warmup", "2", "--comm", "host", "--other", "0", "--cpu-runs", "0",
             "--cpu-seconds", "0", "--frontend", "0", "--solve-all", "0", "--model-scaling", "0", "--weak", "0"]
     if launch == "torchrun":

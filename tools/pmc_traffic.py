@@ -46,7 +46,7 @@ def main():
         groups["%s@grid%d" % (name, grid)] = {
             "kernel": name, "grid_size": grid, "dispatches": n, "active_dispatches": len(act),
             "fetch_bytes": fb, "write_bytes": wb, "traffic_bytes": fb + wb}
-    cmd = sys.argv[3] if len(sys.argv) > 3 else "bench.py --steps 20 --warmup 4 --cpu-seconds 0"
+    cmd = sys.argv[3] if len(sys.argv) > 3 else "bench.py --full --steps 20 --warmup 4 --cpu-seconds 0"
     res = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over %s; FETCH_SIZE "
                      "doubled (gfx950), KiB -> bytes" % cmd,
            "kernels": groups}

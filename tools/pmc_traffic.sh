@@ -13,7 +13,7 @@ i=0
 for c in FETCH_SIZE WRITE_SIZE; do
   i=$((i+1))
   timeout -s KILL 240 rocprofv3 --pmc $c --kernel-include-regex "$KRE" -d "$OUT/p$i" -o run --output-format csv \
-    -- python3 "$R/bench.py" --steps 20 --warmup 4 --cpu-seconds 0 > "$OUT/p$i.json" 2> "$OUT/p$i.log" \
+    -- python3 "$R/bench.py" --full --steps 20 --warmup 4 --cpu-seconds 0 > "$OUT/p$i.json" 2> "$OUT/p$i.log" \
     || { echo "pass $c failed"; tail -5 "$OUT/p$i.log"; exit 1; }
 done
 python3 "$R/tools/pmc_traffic.py" "$OUT" "$R/profiles/${TAG}_pmc_traffic.json"
