@@ -194,9 +194,7 @@ __device__ __forceinline__ void chol_candidates(const Dev& d, const double* y, i
 struct CandLds {
   double *q, *t, *sc, *J, *r, *tn;
   int *fb, *fl, *fa, *fbb;   // (a pair's blocks are read through fb[fa], fb[fbb]: no dependent global load)
-  static size_t bytes(int F, int D, int n) {
-    return (size_t)(7 * F + n + 7 * D + 3 * F) * sizeof(double) + (size_t)(2 * F + 2 * D) * sizeof(int);
-  }
+  // (its size: cand_lds_bytes, ba_layout.h)
   __device__ void carve(double* base, int F, int D, int n) {
     q = base; t = q + 4 * F; sc = t + 3 * F; J = sc + n; r = J + 6 * D; tn = r + D;
     fb = reinterpret_cast<int*>(tn + 3 * F); fl = fb + F; fa = fl + F; fbb = fa + D;
@@ -1913,12 +1911,7 @@ __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_
 // The same elimination as k_cholesky_global's arrowhead factorisation, reordered: equal up to rounding.
 // Dynamic LDS (doubles): x [16 NT], z' [16 NT], row flags [NT ints], then (flags bit 0) the q_K tiles [256 NT] and
 // (bit 1) the candidate pass's operands (CandLds, staged by the waves that wait for the chain).
-size_t border_lds_doubles(int NT, int flags, int F, int D, int n) {
-  size_t o = 32 * (size_t)NT + (NT + 1) / 2;
-  if (flags & 1) o += 256 * (size_t)NT;
-  if (flags & 2) o += (CandLds::bytes(F, D, n) + 7) / 8;
-  return o;
-}
+// (border_lds_doubles, ba_layout.h)
 template <bool kQlds>   // (flags bit 0 as a template parameter: a run-time choice of LDS or global compiles to flat accesses)
 __global__ __launch_bounds__(kBordThreads) void k_chol_border(Dev d, double* __restrict__ Wg, int flags) {
   const LmState* st = d.st;
@@ -2239,8 +2232,6 @@ __global__ __launch_bounds__(kBordThreads) void k_chol_border(Dev d, double* __r
 
 // ------------------------------------------------------------------------------------------------
 // host launchers (ba_launch.h)
-
-size_t cand_lds_bytes(int F, int D, int n) { return CandLds::bytes(F, D, n); }
 
 static const void* const kCholTilesKernels[] = {(const void*)k_chol_tiles<false>, (const void*)k_chol_tiles<true>};
 

@@ -22,29 +22,21 @@
 
 #include <cstdint>
 
+#include "ba_layout.h"
+
 namespace sg {
 
-constexpr int kCamV = 27;           // per camera block: upper(Jc^T Jc) 21 + Jc^T r 6
 // Observation record (ba_device.h jidx2): r~ 2 | rotation Jacobian 2x3 | point Jacobian 2x4 = 16 doubles; the
 // translation Jacobian is not stored (J~t = -X.w J~p[:, 0:3], jc_trans)
 constexpr int kJPairs = 8;
 constexpr int kJStride = 2 * kJPairs;
 constexpr int kNScal = 16;          // per-chunk scalar slots
 constexpr int kCholThreads = 512;
-constexpr int kCholNb = 16;
 
 enum ScalSlot {
   kCost = 0, kFail, kFixed, kFixedFail, kXnorm2, kGmax, kLinFail, kModel, kCandCost, kCandFail, kStep2,
   kCandX2
 };
-
-// Packed per-observation facts (device order), so that a sweep lane's loads depend only on its own
-// observation record: camera block + 1 (0: frame not free) in bits 0-15, camera in bits 16-23, then the
-// frame's rotation / translation freedom, the point's freedom and the fixed flag (all blocks constant).
-constexpr int kMetaCamShift = 16;
-constexpr int kMetaRot = 1 << 24, kMetaTrans = 1 << 25, kMetaPfree = 1 << 26, kMetaFixed = 1 << 27;
-__host__ __device__ __forceinline__ int meta_block(int m) { return (m & 0xffff) - 1; }
-__host__ __device__ __forceinline__ int meta_cam(int m) { return (m >> kMetaCamShift) & 0xff; }
 
 // Exchange-buffer scalar slots appended after the camera blocks.
 enum CamX { kXCost = 0, kXFail, kXFixed, kXFixedFail, kXXnorm2, kXNum };
@@ -54,81 +46,8 @@ enum UpdX { kUModel = 0, kUCandCost, kUCandFail, kUStep2, kUCandX2, kULinFail, k
 enum CholX { kCStep2 = 0, kCCandX2, kCModel, kCCandCost, kCFail, kCTimeout, kCNum };
 
 
-// k_schur work decomposition (see ba_solver.hip): a segment is a run of consecutive points (device order)
-// whose camera columns fit a window of <= kSchurTW 16-column tiles of S, one workgroup (kSchurCWaves waves holding
-// the window's upper tiles and rhs rows in MFMA accumulators, a point wave, kSchurCellWaves building the
-// operand tiles); it streams through
-// LDS in batches of <= kSchurBatchPts points whose operand tiles (64 doubles each) fit kSchurXCap.  The cells
-// of a point (one per block of its span) carry its observations.  A point spanning more than kSegNbMax blocks
-// is a WideSeg of its own (observation pairs, global atomics).
-#ifndef SG_SEG_NB
-#define SG_SEG_NB 24   // widest point of a segment, in blocks (6 * 24 + 14 <= 16 * kSchurTW columns)
-#endif
-constexpr int kSegNbMax = SG_SEG_NB;
-static_assert(kSegNbMax <= 24, "cells of a batch: kSchurBatchCells");
-constexpr int kSchurCellWaves = 3;   // operand-tile waves (a batch has <= 64 kSchurCellWaves cells)
-#ifndef SG_SCHUR_CW
-#define SG_SCHUR_CW 4
-#endif
-constexpr int kSchurCWaves = SG_SCHUR_CW;   // MFMA waves (4: one per SIMD; 8: two); a point wave between the groups
-constexpr int kSchurWaves = kSchurCellWaves + 1 + kSchurCWaves;
-constexpr int kSchurThreads = 64 * kSchurWaves;
-#ifndef SG_SCHUR_TW
-#define SG_SCHUR_TW 10   // window width in tiles (variant builds: tools/build_variant.sh)
-#endif
-constexpr int kSchurTW = SG_SCHUR_TW;
-constexpr int kSchurTiles = kSchurTW * (kSchurTW + 1) / 2;
-constexpr int kSchurAug = kSchurTiles + kSchurTW;   // window tiles + one rhs tile per tile row
-constexpr int kSchurTPW = (kSchurAug + kSchurCWaves - 1) / kSchurCWaves;   // accumulator tiles per wave
-constexpr int kSchurXCap = 112 * 64;   // operand tiles (64 doubles each) per batch buffer
-#ifndef SG_SCHUR_BATCH
-#define SG_SCHUR_BATCH 32
-#endif
-constexpr int kSchurBatchPts = SG_SCHUR_BATCH;   // <= 64: a batch's point table is one point per lane
-constexpr int kSchurBatchCells = kSchurBatchPts * 24;   // cells of a batch (spans <= kSegNbMax)
-static_assert(6 * kSegNbMax + 14 <= 16 * kSchurTW, "a widest point must fit the tile window");
-struct SchurSeg {
-  int32_t p0, p1;       // point range
-  int32_t b_lo, nb;     // blocks the points observe: rhs partial [b_lo, b_lo + nb)
-  int32_t s_off;        // S_slab offset: ntw (ntw + 1) / 2 row-major 16x16 tiles, then 6 nb rhs entries
-  int32_t t0, ntw;      // window: tile columns [t0, t0 + ntw) of S
-  int32_t bt0, bt1;     // batches
-  int32_t pad;
-};
-struct SchurBatch {
-  int32_t p0, p1;       // points
-  int32_t c0, c1;       // cells
-};
-struct WideSeg {
-  int32_t p;            // the point
-  int32_t pair_lo, pair_hi;
-  int32_t pad;
-};
-
-// k_linearize work decomposition: a chunk (one single-wave workgroup) is a run of consecutive points whose
-// camera blocks fit one window of <= kLinNbMax blocks, split into rounds of <= kLinObs observations and
-// <= kLinPts points that hold whole points (one observation per lane).  A point with more observations, or
-// spanning more blocks, is a "wide" chunk of its own: rounds are pieces of it and its camera terms go to
-// global atomics.  A chunk's workgroup has one or two waves (BaSolver::lin_waves_, fixed at load: two when the
-// grid would leave SIMDs idle): wave w takes rounds r0 + w, r0 + w + 2, ... into LDS accumulators of its own,
-// summed in wave order at the end (a wide chunk runs on wave 0).
-constexpr int kLinThreads = 64;   // lanes of one wave (one observation per lane)
-constexpr int kLinObs = 64;
-constexpr int kLinPts = 16;
-constexpr int kLinNbMax = 24;
-constexpr int kLinMaxRounds = 4;   // measured best at 130k and 1.6M observations
-struct LinRound {
-  int32_t o0, o1;     // observation range
-  int32_t p0, p1;     // points (whole points; every piece of a wide point names it)
-};
-struct LinChunk {
-  int32_t r0, r1;     // round range
-  int32_t b_lo, nb;   // camera window [b_lo, b_lo + nb) (nb = 0: no camera terms in LDS)
-  int32_t cam_off;    // offset of this chunk's camera partials in cam_slab (doubles)
-  int32_t wide;       // one point: camera terms by global atomics, point block reduced over the workgroup
-  int32_t p0, p1;
-  int32_t u0;         // its first k_point_update work unit (one per round; one for a wide chunk)
-};
+// The work-unit records (SchurSeg, SchurBatch, WideSeg, LinChunk, LinRound), the packed observation word
+// (kMeta*) and the sizes the work lists are cut to: ba_layout.h, shared with the host planner.
 
 // Concurrency contract.  Two launches store the whole LmState from one thread while other workgroups of the
 // SAME launch read it: k_cam_reduce mode 2 (workgroup NB+1 takes the decision while workgroups 0..NB read

@@ -10,7 +10,12 @@
 //                 k_cholesky_window, k_cholesky_global
 //   ba_intr.hip   the free-intrinsics columns of SolveAllFrames(..., true): k_intr_*
 // and the host driver (ba_solver.hip) reaches them only through the launchers below (plain host functions: no
-// kernel symbol crosses a translation unit).
+// kernel symbol crosses a translation unit).  What the kernels read at a load is planned on the host alone:
+//   ba_layout.h   the work-unit records and sizes the planner and the kernels share (no HIP header)
+//   ba_plan.cpp   the load's planner, pure functions of the problem (ba_plan.h), in stages: the order (PlanBlocks,
+//                 PlanPointOrder, PlanObservations), the work lists (PlanSweep, PlanSchur, PlanReduceLists,
+//                 PlanFrameDistance, PlanIntrLists, PlanLoBlk), PlanEnvelope (Cholesky envelope, k_S_reduce tile
+//                 lists) and PlanChol (the Cholesky kernel choice)
 #ifndef SG_BA_LAUNCH_H_
 #define SG_BA_LAUNCH_H_
 
@@ -25,15 +30,9 @@ namespace sg {
 
 // ---- launch geometry the host driver shares with the kernels
 constexpr int kRedThreads = 1024;      // k_cam_reduce / k_upd_reduce workgroup (>= kCamSlices * kCamV)
-constexpr int kCholWS = 128;           // k_cholesky_window: LDS window columns
-constexpr int kCholLd = kCholWS + 1;
+constexpr int kCholLd = kCholWS + 1;    // (kCholWS, kJendSh, kCandMax, kTB, kTileMaxNT, kSplitMinNT: ba_layout.h)
 constexpr size_t kCholLds = (size_t)kCholWS * kCholLd * sizeof(double);
-constexpr int kJendSh = 512;           // panel band ends cached in LDS (n <= 8192)
-constexpr int kCandMax = 1024;         // frames / FrameDistance residuals staged in LDS for the candidate pass
-constexpr int kTB = 8;                 // k_chol_tiles: band width in tiles = waves
 constexpr int kTileThreads = kTB * 64;
-constexpr int kTileMaxNT = 400;        // k_chol_tiles: tile rows (dynamic LDS: x, z' 16 NT doubles each + band ends)
-constexpr int kSplitMinNT = 13;        // dissected band from this many tile rows
 constexpr int kBordThreads = 256;      // k_chol_border
 constexpr int kIntrFkThreads = 256;    // k_intr_fk (the slices per block list stay ~256 observations)
 constexpr int kIntrFinThreads = 256;   // k_intr_fin
@@ -77,8 +76,6 @@ void LaunchIntrStepK(hipStream_t s, const Dev& d);
 // Grant every Cholesky kernel the dynamic LDS it may need, once per solver (a load never changes an attribute):
 // returns the limits granted to k_chol_tiles, k_cholesky_global and k_chol_border.
 void CholSetAttributes(size_t* tile_lds, size_t* gchol_lds, size_t* border_lds);
-size_t border_lds_doubles(int NT, int flags, int F, int D, int n);   // k_chol_border's dynamic LDS (doubles)
-size_t cand_lds_bytes(int F, int D, int n);   // the candidate pass's operands staged in a Cholesky's LDS
 void LaunchCholTilesK(bool stamp, dim3 grid, size_t lds, hipStream_t s, const Dev& d, const int32_t* panel_jend,
                       double* Wg, int32_t* tflag, int nd, int flags);
 void LaunchCholBorderK(int border_flags, size_t lds, hipStream_t s, const Dev& d, double* Wg);

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "ba_kernels.h"
+#include "ba_plan.h"
 #include "common.h"
 #include "dbuf.h"
 #include "hostio.h"
@@ -71,22 +72,20 @@ class BaSolver {
   bool idle_valid_ = false;
   void MarkIdle(hipStream_t s);
   void DevMark(hipStream_t s, int i);
+  std::string LoadDeviceTimes(std::chrono::steady_clock::time_point load_t0, bool idle_valid_prev,
+                              double idle_gap_host);
   bool need_seq_ = true;   // the next iteration is the first of a solve (it computes the camera scale)
   std::unique_ptr<Comm> comm_;
   bool loaded_ = false;
   bool began_ = false;
-  bool chol_window_ = true;
-  bool chol_tiles_ = false;    // tiled register-resident band Cholesky (k_chol_tiles)
-  bool chol_border_ = false;   // free intrinsics: k_chol_tiles on the frame band, then k_chol_border
-  int border_flags_ = 0;       // its LDS placements (bit 0 q_K tiles, bit 1 candidate operands)
-  size_t border_lds_max_ = 0;  // its dynamic LDS limit
-  size_t tile_lds_ = 0;        // its dynamic LDS
-  DBuf<double> Wg_;            // its back-substitution tiles W_KJ = U_KK^-1 U_KJ (+ the bottom half's)
-  int chol_nd_ = 0;            // dissected band: tile rows the second workgroup factors bottom-up (0: one WG)
-  int chol_ns_ = 7;            // ... and the separator's tile rows (<= 7)
+  // what the last full load planned (ba_plan.h): the Cholesky kernel choice and the counts of the work lists
+  // and of the envelope
+  CholPlan chol_;
+  WorkCounts wk_;
+  EnvCounts env_;
+  size_t border_lds_max_ = 0;  // k_chol_border's dynamic LDS limit
+  DBuf<double> Wg_;            // k_chol_tiles' back-substitution tiles W_KJ = U_KK^-1 U_KJ (+ the bottom half's)
   DBuf<int32_t> tflag_;        // dissected band hand-off counters {bottom done, top done}
-  bool chol_cand_lds_ = false;   // candidate-pass operands staged in the Cholesky's LDS (small problems)
-  int s_lstride_ = 256, r_lstride_ = 256;   // k_S_reduce's padded list rows (Dev::s_lstride / r_lstride)
   // tests only: force the dissected Cholesky's separator wait to time out (k_chol_tiles flags bit 2)
   bool chol_force_tmo_ = getenv("SG_CHOL_FORCE_TIMEOUT") && atoi(getenv("SG_CHOL_FORCE_TIMEOUT")) != 0;
   // SG_CHOL_ZPRE=0: k_chol_tiles factors D_0 itself instead of starting from k_S_reduce's Z_0 (A/B, tests)
@@ -105,12 +104,10 @@ class BaSolver {
   int32_t nallreduce_ = 0;   // landmark-shard all-reduces issued (sg_ba_info.num_allreduces)
   // tests: issue the communicator's collectives on one rank too (SG_COMM_FORCE=1: RCCL with one rank is a copy)
   bool comm_force_ = getenv("SG_COMM_FORCE") && atoi(getenv("SG_COMM_FORCE")) == 1;
-  size_t npack_ = 0;                                      // band of S + rhs, doubles (all-reduce size)
   bool stamp_on_ = false;
   int ncu_ = 256;                       // compute units (Schur segment count), queried once
   size_t tile_lds_set_ = 0;             // dynamic LDS last granted to k_chol_tiles
   size_t gchol_lds_max_ = 0;            // dynamic LDS granted to k_cholesky_global
-  bool chol_gstage_ = false;            // k_cholesky_global stages panel rows in LDS
   std::unique_ptr<class Stager> stager_;   // batched structure uploads (stager.h)
   DBuf<unsigned long long> stamps_;
 
@@ -123,8 +120,6 @@ class BaSolver {
   int F_ = 0, P_ = 0, M_ = 0, NB_ = 0, n_ = 0, D_ = 0, ncam_ = 0;
   std::vector<int32_t> point_perm_;   // device order -> problem point
   std::vector<int32_t> obs_perm_;     // device order -> problem observation
-  int band_tiles_ = 0;     // widest Cholesky envelope row (16-wide tiles)
-  size_t npairs_ = 0;      // Schur observation pairs
   // Incremental problem update (replacing the per-call rebuild of slam.cpp:257-414):
   // the structure of the last Load.  A Load with the same structure (frames, cameras, freedom flags,
   // observation -> frame / point incidence, FrameDistance pairs) keeps the point order, the CSR, the sweep
@@ -166,23 +161,15 @@ class BaSolver {
   DBuf<double> Jk_, KU_, kst_;     // free intrinsics (nk_ > 0)
   DBuf<double> Yk_, kpart_;        //   W_kp V~p^-1 per point and camera; per-block camera sums
   DBuf<int32_t> intr_boff_, intr_bidx_;   //   per-block observation lists
-  int intr_nsl_ = 1;                      //   k_intr_fk workgroups per block list
   int nk_ = 0;                     // 7 * cameras when the intrinsics are free
   double stab_b_ = 25.0;
   DBuf<SchurSeg> segs_;
   DBuf<LinChunk> lchunks_d_;
   DBuf<LinRound> lrounds_d_;
   DBuf<double> lin_scal_;
-  int nlin_ = 0;
-  int lin_waves_ = 1;   // waves per k_linearize / k_update_lin chunk (2 when 2 nlin_ waves fit the chip at once)
   void LaunchLinearize(const Dev& d);
   void LaunchUpdateLin(const Dev& d);
-  int npu_ = 0;
   DBuf<double> seg_fail_;
-  int nseg_ = 0, nwide_ = 0, nstile_ = 0;
-  double schur_mfma_ = 0.0;   // v_mfma_f64_16x16x4f64 tile updates per k_schur launch (KernelWork)
-  double schur_rhs_ = 0.0;    // v_mfma_f64_4x4x4_4b_f64 rhs updates per k_schur launch
-  double schur_useful_ = 0.0; // flops of the slots that multiply each point's own tiles (no zero tiles)
   DBuf<SchurBatch> sbatch_;
   DBuf<WideSeg> wsegs_;
   DBuf<int32_t> pinfo_, pmx_, cells_, cell_obs_, stile_;

@@ -1,7 +1,7 @@
 // ba_solver.hip — host driver of the MI355X-native Levenberg-Marquardt bundle adjustment (the reference's
 // Slam::Run, slam.cpp:482-521, which hands the problem to Ceres 1.8 with SPARSE_SCHUR; restated on gfx950):
-// problem load (work lists, the Schur segments, the Cholesky envelope, the structure-only incremental path), the
-// per-iteration kernel chain and the host polls.  The kernels are in the family translation units listed in
+// problem load (the lists planned by ba_plan.cpp uploaded, the buffers sized, the structure-only incremental
+// path), the per-iteration kernel chain and the host polls.  The kernels are in the family translation units listed in
 // ba_launch.h; this file launches them through ba_launch.h's launchers and keeps only a few utility kernels
 // (copies, buffer resets, the state hand-off, the solution download).
 //
@@ -53,12 +53,12 @@ static const char* kKernelNames[kKNum] = {"linearize", "cam_reduce", "cam_finali
 
 void BaSolver::LaunchCholTiles(bool stamp, dim3 grid, const Dev& d, int flags) {
   // bordered: the frame band ends follow the arrowhead's panel ends in work_i_
-  const int32_t* pj = (const int32_t*)work_i_.ptr + (chol_border_ ? (n_ + kCholNb - 1) / kCholNb : 0);
-  if (chol_border_) flags |= 8;
-  LaunchCholTilesK(stamp, grid, tile_lds_, stream_, d, pj, Wg_.ptr, tflag_.ptr, chol_nd_, flags | (chol_ns_ << 8));
-  if (chol_border_) {
+  const int32_t* pj = (const int32_t*)work_i_.ptr + (chol_.border ? (n_ + kCholNb - 1) / kCholNb : 0);
+  if (chol_.border) flags |= 8;
+  LaunchCholTilesK(stamp, grid, chol_.tile_lds, stream_, d, pj, Wg_.ptr, tflag_.ptr, chol_.nd, flags | (chol_.ns << 8));
+  if (chol_.border) {
     const int ntf = (6 * NB_ + kCholNb - 1) / kCholNb;
-    LaunchCholBorderK(border_flags_, border_lds_doubles(ntf, border_flags_, F_, D_, n_) * sizeof(double), stream_, d,
+    LaunchCholBorderK(chol_.border_flags, border_lds_doubles(ntf, chol_.border_flags, F_, D_, n_) * sizeof(double), stream_, d,
                       Wg_.ptr);
   }
 }
@@ -134,6 +134,60 @@ __global__ __launch_bounds__(256) void k_fill_obs_pnt(const int32_t* __restrict_
   for (int o = poff[i]; o < poff[i + 1]; ++o) obs_pnt[o] = i;
 }
 
+// The knobs of a full load, read at every one (A/B switches and tests: DESIGN.md).
+static LoadKnobs ReadLoadKnobs() {
+  auto is = [](const char* name, int v) { return getenv(name) && atoi(getenv(name)) == v; };
+  LoadKnobs k;
+  if (const char* e = getenv("SG_LIN_WAVES")) k.lin_waves = atoi(e) == 2 ? 2 : 1;
+  k.chol_gstage = !is("SG_CHOL_GSTAGE", 0);
+  k.chol_window = getenv("SG_CHOL_WINDOW") != nullptr;
+  k.chol_border = !is("SG_CHOL_BORDER", 0);
+  k.chol_split = !is("SG_CHOL_SPLIT", 0);
+  k.chol_sep7 = is("SG_CHOL_SEP", kTB - 1);
+  k.stamp = getenv("SG_STAMP") && getenv("SG_STAMP")[0] == '1';
+  return k;
+}
+
+// SG_HOST_TIMING: the device's share of a full load (the marks Load set), against the host's wall time.
+std::string BaSolver::LoadDeviceTimes(std::chrono::steady_clock::time_point load_t0, bool idle_valid_prev,
+                                      double idle_gap_host) {
+  std::string log;
+  float a = 0, b = 0, c = 0;
+  (void)hipEventElapsedTime(&a, dev_marks_[0], dev_marks_[1]);
+  (void)hipEventElapsedTime(&b, dev_marks_[1], dev_marks_[2]);
+  (void)hipEventElapsedTime(&c, dev_marks_[2], dev_marks_[3]);
+  float e = 0;
+  (void)hipEventElapsedTime(&e, dev_marks_[4], dev_marks_[3]);
+  const double hw = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - load_t0).count();
+  char buf[320];
+  snprintf(buf, sizeof(buf), " [device: batch1..batch2 %.2f, scatter2 %.2f, reset %.2f; load start..reset: device "
+           "%.2f, host %.2f]", a, b, c, e, hw);
+  log += buf;
+  if (idle_valid_prev) {
+    float g = 0;
+    const hipError_t ge = hipEventElapsedTime(&g, ev_idle_prev_, dev_marks_[4]);
+    snprintf(buf, sizeof(buf), " [last idle..load start: device %.2f (%d), host %.2f]", g, (int)ge, idle_gap_host);
+    log += buf;
+  }
+  snprintf(buf, sizeof(buf), " (staged %.2f MB; device allocations so far %ld)", stager_->staged_bytes() / 1e6,
+           g_dbuf_allocs.load());
+  log += buf;
+  return log;
+}
+
+// What the device solver's packed indices hold (beyond ValidateProblem's checks of the problem itself).
+static void ValidateDeviceLimits(const sg_problem& p, int nranks) {
+  SG_REQUIRE(!p.cameras_free || (p.num_cameras <= kMaxIntrCams && nranks == 1), SG_EINVAL,
+             "free intrinsics: at most 4 cameras, on one rank (landmark shards keep the intrinsics constant)");
+  SG_REQUIRE(p.num_cameras <= 0xff, SG_EINVAL, "too many cameras for the device solver");
+  int nfree = 0;
+  for (int f = 0; f < p.num_frames; ++f) nfree += (p.frame_rot_free[f] || p.frame_trans_free[f]) ? 1 : 0;
+  SG_REQUIRE(nfree < 0xffff, SG_EINVAL, "too many free frames for the device solver");
+  std::vector<int32_t> cnt(p.num_points, 0);
+  for (int o = 0; o < p.num_obs; ++o)
+    SG_REQUIRE(++cnt[p.obs_point[o]] < 65536, SG_EINVAL, "a point has 65536 or more observations");
+}
+
 void BaSolver::Load(const sg_problem& p) {
   static const bool host_timing = getenv("SG_HOST_TIMING") != nullptr;   // development aid: phase times
   auto lt0 = std::chrono::steady_clock::now();
@@ -163,15 +217,7 @@ void BaSolver::Load(const sg_problem& p) {
     std::string verr;
     try {
       ValidateProblem(&p);
-      SG_REQUIRE(!p.cameras_free || (p.num_cameras <= kMaxIntrCams && nranks() == 1), SG_EINVAL,
-                 "free intrinsics: at most 4 cameras, on one rank (landmark shards keep the intrinsics constant)");
-      SG_REQUIRE(p.num_cameras <= 0xff, SG_EINVAL, "too many cameras for the device solver");
-      int nfree = 0;
-      for (int f = 0; f < p.num_frames; ++f) nfree += (p.frame_rot_free[f] || p.frame_trans_free[f]) ? 1 : 0;
-      SG_REQUIRE(nfree < 0xffff, SG_EINVAL, "too many free frames for the device solver");
-      std::vector<int32_t> cnt(p.num_points, 0);
-      for (int o = 0; o < p.num_obs; ++o)
-        SG_REQUIRE(++cnt[p.obs_point[o]] < 65536, SG_EINVAL, "a point has 65536 or more observations");
+      ValidateDeviceLimits(p, nranks());
     } catch (const Error& e) {
       vcode = e.code;
       verr = e.what();
@@ -209,104 +255,18 @@ void BaSolver::Load(const sg_problem& p) {
   range_b_ = p.range * p.range;
   fd_target_ = p.dist_target;
   fd_b2_ = p.dist_range * p.dist_range;
-  // camera blocks: every frame with a free rotation or translation
-  std::vector<int32_t> frame_block(F_, -1);
-  NB_ = 0;
-  for (int f = 0; f < F_; ++f)
-    if (p.frame_rot_free[f] || p.frame_trans_free[f]) frame_block[f] = NB_++;
-  nk_ = p.cameras_free ? 7 * ncam_ : 0;
-  n_ = 6 * NB_ + nk_;   // frame columns, then the free intrinsics
   stab_b_ = p.stab_range * p.stab_range;
+  const LoadKnobs knobs = ReadLoadKnobs();
+  // The lists are planned on the host alone (ba_plan.h); this function uploads them and sizes the buffers.
+  Order ord;
+  PlanBlocks(p, &ord);
+  NB_ = ord.NB;
+  nk_ = ord.nk;
+  n_ = ord.n;
   lap("blocks");
-  // point order: by first free block (points without free-frame observations last)
-  std::vector<int32_t> pfirst(P_, NB_), plast(P_, -1), pcount(P_, 0);
-  for (int o = 0; o < M_; ++o) {
-    const int pt = p.obs_point[o], b = frame_block[p.obs_frame[o]];
-    pcount[pt]++;
-    if (b >= 0) {
-      pfirst[pt] = std::min(pfirst[pt], b);
-      plast[pt] = std::max(plast[pt], b);
-    }
-  }
-  // stable counting sort on the key pfirst in [0, NB]
-  point_perm_.resize(P_);
-  std::vector<int32_t> inv_perm(P_);
-  {
-    std::vector<int32_t> bstart(NB_ + 2, 0);
-    for (int i = 0; i < P_; ++i) bstart[pfirst[i] + 1]++;
-    for (int b = 0; b <= NB_; ++b) bstart[b + 1] += bstart[b];
-    for (int i = 0; i < P_; ++i) {
-      const int pos = bstart[pfirst[i]]++;
-      point_perm_[pos] = i;
-      inv_perm[i] = pos;
-    }
-  }
-  // the first / last free block of each point in device order (the work-list builders below read them per point)
-  std::vector<int32_t> dfirst(P_), dlast(P_);
-  for (int i = 0; i < P_; ++i) {
-    dfirst[i] = pfirst[point_perm_[i]];
-    dlast[i] = plast[point_perm_[i]];
-  }
+  PlanPointOrder(p, &ord);
   lap("point-order");
-  // observations: CSR by device point order (stable in problem order)
-  std::vector<int32_t> poff(P_ + 1, 0);
-  for (int o = 0; o < M_; ++o) poff[inv_perm[p.obs_point[o]] + 1]++;
-  for (int i = 0; i < P_; ++i) poff[i + 1] += poff[i];
-  obs_perm_.assign(M_, 0);
-  {
-    std::vector<int32_t> fill(poff.begin(), poff.end() - 1);
-    for (int o = 0; o < M_; ++o) obs_perm_[fill[inv_perm[p.obs_point[o]]]++] = o;
-    // within a point: observations of constant frames first, then by camera block (stable), so that a point
-    // observed once in every block of its span finds the observation of block b at a fixed offset (k_schur)
-    // (a stable insertion sort: a point has a handful of observations, and std::stable_sort allocates a
-    // buffer per call)
-    for (int i = 0; i < P_; ++i) {
-        int32_t* v = obs_perm_.data() + poff[i];
-        const int k = poff[i + 1] - poff[i];
-        if (k > 64) {
-          std::stable_sort(v, v + k, [&](int a, int b) {
-            return frame_block[p.obs_frame[a]] < frame_block[p.obs_frame[b]];
-          });
-          continue;
-        }
-        for (int x = 1; x < k; ++x) {
-          const int32_t o = v[x];
-          const int key = frame_block[p.obs_frame[o]];
-          int y = x - 1;
-          while (y >= 0 && frame_block[p.obs_frame[v[y]]] > key) {
-            v[y + 1] = v[y];
-            --y;
-          }
-          v[y + 1] = o;
-        }
-      }
-  }
-  std::vector<double> obs_pt(2 * (size_t)M_);
-  std::vector<int32_t> obs_frame(M_);
-  std::vector<uint8_t> obs_fixed(M_), pfree(P_);
-  std::vector<double> X(4 * (size_t)P_);
-  for (int i = 0; i < P_; ++i) {
-    const int pt = point_perm_[i];
-    pfree[i] = p.point_free[pt];
-    for (int a = 0; a < 4; ++a) X[4 * i + a] = p.X[4 * pt + a];
-  }
-  std::vector<int32_t> obs_meta(M_);
-  {
-    // per frame: the frame part of the packed observation word
-    std::vector<int32_t> fmeta(F_);
-    for (int f = 0; f < F_; ++f)
-      fmeta[f] = (frame_block[f] + 1) | (p.frame_camera[f] << kMetaCamShift) | (p.frame_rot_free[f] ? kMetaRot : 0) |
-                 (p.frame_trans_free[f] ? kMetaTrans : 0);
-    for (int o = 0; o < M_; ++o) {
-      const int src = obs_perm_[o], f = p.obs_frame[src];
-      const bool pf = p.point_free[p.obs_point[src]] != 0;
-      obs_pt[2 * o] = p.obs_pt[2 * src];
-      obs_pt[2 * o + 1] = p.obs_pt[2 * src + 1];
-      obs_frame[o] = f;
-      obs_fixed[o] = frame_block[f] < 0 && !pf && !p.cameras_free;
-      obs_meta[o] = fmeta[f] | (pf ? kMetaPfree : 0) | (obs_fixed[o] ? kMetaFixed : 0);
-    }
-  }
+  PlanObservations(p, &ord);
   lap("obs-csr");
   // upload batch 1 — poses, intrinsics, points (current slot; the candidate slot is a device copy) and the
   // observation arrays: its pinned copy and DMA overlap the host's work-list construction below (stager.h)
@@ -317,17 +277,17 @@ void BaSolver::Load(const sg_problem& p) {
               ncam_ > 0 ? std::vector<double>(p.k, p.k + 7 * ncam_) : std::vector<double>{0.0});
   stg.AddInto(q_, 8 * (size_t)F_, std::vector<double>(p.q, p.q + 4 * F_));
   stg.AddInto(t_, 6 * (size_t)F_, std::vector<double>(p.t, p.t + 3 * F_));
-  stg.AddInto(X_, 8 * (size_t)P_, X);
+  stg.AddInto(X_, 8 * (size_t)P_, ord.X);
   stg.Add(frame_cam_, std::vector<int32_t>(p.frame_camera, p.frame_camera + F_));
-  stg.Add(frame_block_, frame_block);
+  stg.Add(frame_block_, ord.frame_block);
   stg.Add(rot_free_, std::vector<uint8_t>(p.frame_rot_free, p.frame_rot_free + F_));
   stg.Add(trans_free_, std::vector<uint8_t>(p.frame_trans_free, p.frame_trans_free + F_));
-  stg.Add(pfree_, pfree);
-  stg.Add(poff_, poff);
-  stg.Add(obs_pt_, obs_pt);
-  stg.Add(obs_frame_, obs_frame);
-  stg.Add(obs_fixed_, obs_fixed);
-  stg.Add(obs_meta_, obs_meta.empty() ? std::vector<int32_t>{0} : obs_meta);
+  stg.Add(pfree_, ord.pfree);
+  stg.Add(poff_, ord.poff);
+  stg.Add(obs_pt_, ord.obs_pt);
+  stg.Add(obs_frame_, ord.obs_frame);
+  stg.Add(obs_fixed_, ord.obs_fixed);
+  stg.Add(obs_meta_, ord.obs_meta);
   if (host_timing) DevMark(s, 0);
   stg.Flush(s);
   {
@@ -349,543 +309,69 @@ void BaSolver::Load(const sg_problem& p) {
     SG_HIP_CHECK(hipGetLastError());
   }
   lap("upload-1");
-  // Schur work lists (see SchurSeg): the cells of every free point (one per block of its span, with the
-  // point's observations in that block), segments of consecutive points whose columns fit kSchurTW tiles of
-  // S, their batches, and each wide point's observation pairs (s <= t, both on free frames).
-  std::vector<int32_t> pinfo(2 * (size_t)std::max(P_, 1), 0), pmx(4 * (size_t)std::max(P_, 1), 0), cells, cell_obs;
-  std::vector<SchurSeg> segs;
-  std::vector<SchurBatch> sbatch;
-  std::vector<WideSeg> wsegs;
-  std::vector<int32_t> pairs_flat;   // int2 per pair (wide points)
-  int s_off = 0;
-  // k_linearize decomposition (see LinChunk): rounds of whole points (<= kLinObs observations), up to
-  // maxr rounds per chunk sharing one camera window; fewer rounds per chunk on small problems so that the
-  // grid still fills the chip.
-  std::vector<LinRound> lrounds;
-  std::vector<LinChunk> lchunks;
-  int lcam_off = 0;
-  {
-    int maxr = std::max(1, std::min(kLinMaxRounds, M_ / (kLinObs * 1024)));
-    auto kobs = [&](int i) { return poff[i + 1] - poff[i]; };
-    auto constonly = [&](int i) { return dfirst[i] >= NB_; };
-    auto pspan = [&](int i) { return constonly(i) ? 0 : dlast[i] - dfirst[i] + 1; };
-    for (int i = 0; i < P_;) {
-      LinChunk c{};
-      c.p0 = i;
-      c.r0 = (int)lrounds.size();
-      if (kobs(i) > kLinObs || pspan(i) > kLinNbMax) {
-        c.wide = 1;
-        for (int o = poff[i]; o < poff[i + 1]; o += kLinObs)
-          lrounds.push_back(LinRound{o, std::min(o + kLinObs, poff[i + 1]), i, i + 1});
-        c.p1 = ++i;
-      } else {
-        const bool co = constonly(i);
-        int lo = co ? 0 : dfirst[i], hi = co ? -1 : dlast[i];
-        int j = i, nr = 0;
-        LinRound R{poff[i], poff[i], i, i};
-        while (j < P_) {
-          if (kobs(j) > kLinObs || pspan(j) > kLinNbMax || constonly(j) != co) break;
-          int l2 = lo, h2 = hi;
-          if (!co) {
-            l2 = std::min(lo, dfirst[j]);
-            h2 = std::max(hi, dlast[j]);
-            if (h2 - l2 + 1 > kLinNbMax) break;
-          }
-          if (R.o1 - R.o0 + kobs(j) > kLinObs || R.p1 - R.p0 >= kLinPts) {
-            if (nr + 1 >= maxr) break;
-            lrounds.push_back(R);
-            ++nr;
-            R = LinRound{poff[j], poff[j], j, j};
-          }
-          R.o1 += kobs(j);
-          R.p1 = j + 1;
-          lo = l2;
-          hi = h2;
-          ++j;
-        }
-        lrounds.push_back(R);
-        c.p1 = j;
-        c.b_lo = lo;
-        c.nb = co ? 0 : hi - lo + 1;
-        i = j;
-      }
-      c.r1 = (int)lrounds.size();
-      c.cam_off = lcam_off;
-      lcam_off += c.nb * kCamV;
-      lchunks.push_back(c);
-    }
-  }
-  nlin_ = (int)lchunks.size();
-  // two waves per chunk (its rounds split between them) while the doubled grid still fits the chip at three
-  // waves per SIMD (k_linearize's occupancy): config 2's ~1.5 k chunks; one wave per chunk when there are more
-  // chunks than that (config 5, the scaled sweep), where the second wave only adds the combine.  (A producer /
-  // consumer split of a chunk's rounds over two waves was measured slower at config 5: DESIGN.md 8.)
-  lin_waves_ = 2 * (long long)nlin_ <= 12LL * ncu_ ? 2 : 1;
-  if (const char* e = getenv("SG_LIN_WAVES")) lin_waves_ = atoi(e) == 2 ? 2 : 1;   // A/B and tests
-  std::vector<int32_t> pu_units;   // k_point_update work units: a round index, or -(chunk + 1) for wide chunks
-  for (int c = 0; c < nlin_; ++c) {
-    lchunks[c].u0 = (int)pu_units.size();   // k_update_lin writes the units' scalars
-    if (lchunks[c].wide)
-      pu_units.push_back(-(c + 1));
-    else
-      for (int r = lchunks[c].r0; r < lchunks[c].r1; ++r) pu_units.push_back(r);
-  }
-  npu_ = (int)pu_units.size();
-  if (pu_units.empty()) pu_units.push_back(0);
+  WorkLists wl;
+  PlanSweep(ord, ncu_, knobs.lin_waves, &wl);
   lap("lin-lists");
-  std::vector<int32_t> obs_blk(M_);
-  for (int o = 0; o < M_; ++o) obs_blk[o] = frame_block[obs_frame[o]];
-  // span in blocks of a free point's Schur terms (0: none)
-  std::vector<int32_t> ssp(std::max(P_, 1));
-  for (int i = 0; i < P_; ++i) ssp[i] = (pfree[i] && dfirst[i] < NB_) ? dlast[i] - dfirst[i] + 1 : 0;
-  auto sspan = [&](int i) { return ssp[i]; };
-  std::vector<int32_t> simple_obs(std::max(P_, 1), -1);   // observation of the first block if one per block
-  int ncell = 0;
-  npairs_ = 0;
-  schur_mfma_ = 0.0;
-  schur_rhs_ = 0.0;
-  schur_useful_ = 0.0;
-  {
-    std::vector<std::pair<int, int>> bo;
-    cells.reserve(4 * (size_t)M_ + 4);
-    cell_obs.reserve((size_t)M_ / 4 + 1);
-    for (int i = 0; i < P_; ++i) {
-      size_t kb = 0;
-      for (int o = poff[i]; o < poff[i + 1]; ++o) kb += obs_blk[o] >= 0;
-      if (pfree[i]) npairs_ += kb * (kb + 1) / 2;
-      const int sp = sspan(i);
-      if (sp == 0 || sp > kSegNbMax) continue;
-      const int pf = dfirst[i];
-      pinfo[2 * i] = (int)(cells.size() / 4);
-      pinfo[2 * i + 1] = (pf << 8) | sp;
-      bo.clear();
-      for (int o = poff[i]; o < poff[i + 1]; ++o)
-        if (obs_blk[o] >= 0) bo.emplace_back(obs_blk[o], o);
-      if (!std::is_sorted(bo.begin(), bo.end())) std::sort(bo.begin(), bo.end());   // sorted at load already
-      {
-        bool one = (int)bo.size() == sp;   // observations sorted by block at load: consecutive
-        for (int q = 0; one && q < sp; ++q) one = bo[q].first == pf + q && bo[q].second == bo[0].second + q;
-        if (one) simple_obs[i] = bo[0].second;
-      }
-      size_t k = 0;
-      for (int b = pf; b < pf + sp; ++b) {
-        // {first observation or -1, point, (block << 16) | further observations, their offset in cell_obs}
-        int o0 = -1;
-        if (k < bo.size() && bo[k].first == b) o0 = bo[k++].second;
-        const int k1 = (int)cell_obs.size();
-        while (k < bo.size() && bo[k].first == b) cell_obs.push_back(bo[k++].second);
-        cells.insert(cells.end(), {o0, i, (int)(((unsigned)b << 16) | (unsigned)(cell_obs.size() - k1)), k1});
-      }
-    }
-    ncell = (int)cells.size() / 4;
-    if (cells.empty()) cells.assign(4, 0);
-    if (cell_obs.empty()) cell_obs.push_back(0);
-  }
-  {
-    // Segments: one per CU (the workgroup's LDS holds one per CU; fewer, longer segments write fewer partial tiles
-    // and keep the producer/consumer pipeline full: 256 / 384 / 512 / 768 / 1024 segments measured 35.9 / 46.5 /
-    // 40.9 / 47.8 / 53.0 us at C2, profiles/r2 segs sweep), balanced by the work of the busiest MFMA wave rather
-    // than by point count (round 5): a point costs its slots on that wave, ceil(schur_aug_base(jhi + 1) /
-    // kSchurCWaves) with jhi its last tile in the segment's window, plus kSegPointCost for its fetch (the MFMA
-    // waves are the bound once the producers are pipelined; 0 / 1 / 2 / 4 / 8 measured C5 k_schur 292 / 260 /
-    // 245 / 238 / 244 us against 259 with equal point counts, profiles/r5_s1_schur_ab.log).  The cap starts at the
-    // estimated total / CUs (each point's tiles counted from its own first tile) and is raised while the window
-    // breaks push the count past the CUs: two passes at C2 and C5.
-    constexpr int kSegMinPts = 16;      // small problems: no segment of a handful of points
-    constexpr int kSegPointCost = 4;
-    auto point_cost = [&](int j, int tile0) {
-      const int sp = sspan(j);
-      if (sp == 0) return kSegPointCost;
-      const int e = (6 * (dfirst[j] + sp) - 1) / 16 - tile0;
-      return kSegPointCost + (schur_aug_base(e + 1) + kSchurCWaves - 1) / kSchurCWaves;
-    };
-    std::vector<int32_t> seg_end;   // exclusive end of each planned segment, in point order
-    auto plan = [&](long long cap) {
-      seg_end.clear();
-      for (int i = 0; i < P_;) {
-        if (sspan(i) > kSegNbMax) {   // a wide point: k_schur_wide (the build loop below)
-          ++i;
-          continue;
-        }
-        int clo = INT32_MAX, chi = -1, j = i;
-        long long acc = 0;
-        while (j < P_) {
-          const int sp = sspan(j);
-          if (sp > kSegNbMax) break;
-          int l2 = clo, h2 = chi;
-          if (sp > 0) {
-            const int pf = dfirst[j];
-            l2 = std::min(clo, 6 * pf);
-            h2 = std::max(chi, 6 * (pf + sp));
-            if ((h2 + 15) / 16 - l2 / 16 > kSchurTW) break;
-          }
-          const int c = point_cost(j, l2 == INT32_MAX ? 0 : l2 / 16);
-          if (j - i >= kSegMinPts && acc + c > cap) break;
-          acc += c;
-          clo = l2;
-          chi = h2;
-          ++j;
-        }
-        seg_end.push_back(j);
-        i = j;
-      }
-    };
-    {
-      long long est = 0;
-      for (int j = 0; j < P_; ++j)
-        if (sspan(j) <= kSegNbMax) est += point_cost(j, sspan(j) ? 6 * dfirst[j] / 16 : 0);
-      long long cap = std::max(1LL, (est + ncu_ - 1) / ncu_);
-      for (int pass = 0; pass < 8; ++pass) {
-        plan(cap);
-        if ((int)seg_end.size() <= ncu_) break;
-        cap += cap * (seg_end.size() - ncu_) * 3 / (2 * ncu_) + cap / 200 + 1;
-      }
-    }
-    size_t next_seg = 0;
-    int cnext = 0;
-    for (int i = 0; i < P_;) {
-      if (sspan(i) > kSegNbMax) {
-        WideSeg w{};
-        w.p = i;
-        w.pair_lo = (int)pairs_flat.size() / 2;
-        for (int os = poff[i]; os < poff[i + 1]; ++os) {
-          if (obs_blk[os] < 0) continue;
-          for (int ot = os; ot < poff[i + 1]; ++ot) {
-            if (obs_blk[ot] < 0) continue;
-            pairs_flat.push_back(((os - poff[i]) << 16) | (ot - poff[i]));
-            pairs_flat.push_back((obs_blk[os] << 16) | obs_blk[ot]);
-          }
-        }
-        w.pair_hi = (int)pairs_flat.size() / 2;
-        wsegs.push_back(w);
-        ++i;
-        continue;
-      }
-      SchurSeg sg{};
-      sg.p0 = i;
-      int clo = INT32_MAX, chi = -1, blo = INT32_MAX, bhi = -1;   // columns [clo, chi), blocks [blo, bhi]
-      int j = i;
-      SG_REQUIRE(next_seg < seg_end.size() && seg_end[next_seg] > i, SG_EINVAL, "Schur segment plan out of step");
-      const int jend = seg_end[next_seg++];
-      while (j < jend) {
-        const int sp = sspan(j);
-        if (sp > kSegNbMax) break;
-        if (sp > 0) {
-          const int pf = dfirst[j];
-          const int l2 = std::min(clo, 6 * pf), h2 = std::max(chi, 6 * (pf + sp));
-          if ((h2 + 15) / 16 - l2 / 16 > kSchurTW) break;
-          clo = l2;
-          chi = h2;
-          blo = std::min(blo, pf);
-          bhi = std::max(bhi, pf + sp - 1);
-        }
-        ++j;
-      }
-      sg.p1 = j;
-      if (chi >= 0) {
-        sg.t0 = clo / 16;
-        sg.ntw = (chi + 15) / 16 - sg.t0;
-        sg.b_lo = blo;
-        sg.nb = bhi - blo + 1;
-      }
-      // k_schur's asm chain (schur_chain.h) is entered at an offset computed from a point's last window tile:
-      // every point must end inside the window (jhi <= kSchurTW - 1)
-      SG_REQUIRE(sg.ntw <= kSchurTW, SG_EINVAL, "Schur segment window wider than kSchurTW");
-      sg.s_off = s_off;
-      s_off += sg.ntw * (sg.ntw + 1) / 2 * 256 + 16 * sg.ntw;
-      // last window tile of each point's columns (-1: no Schur terms)
-      auto pjhi = [&](int k) {
-        const int sp = sspan(k);
-        return sp == 0 ? -1 : (6 * (dfirst[k] + sp) - 1 - 16 * sg.t0) / 16;
-      };
-      sg.bt0 = (int)sbatch.size();
-      for (int k = i; k < j;) {
-        SchurBatch B{};
-        B.p0 = k;
-        B.c0 = cnext;
-        int nc = 0, nx = 0;
-        while (k < j && k - B.p0 < kSchurBatchPts && nx + 64 * (pjhi(k) + 1) <= kSchurXCap &&
-               nc + sspan(k) <= 64 * kSchurCellWaves) {
-          SG_REQUIRE(pjhi(k) < sg.ntw, SG_EINVAL, "point ends outside its Schur segment window");
-          pmx[4 * k] = nx;
-          pmx[4 * k + 1] = pjhi(k);
-          pmx[4 * k + 2] = simple_obs[k];
-          pmx[4 * k + 3] = nc;
-          nx += 64 * (pjhi(k) + 1);
-          schur_mfma_ += schur_aug_base(pjhi(k) + 1) - (pjhi(k) + 1);   // window tiles (16x16x4)
-          schur_rhs_ += pjhi(k) + 1;                                      // rhs slots (4x4x4, 4 blocks)
-          if (pjhi(k) >= 0) {   // the slots that multiply the point's own tiles (the rest multiply zeros)
-            const double nu = pjhi(k) - (6 * dfirst[k] - 16 * sg.t0) / 16 + 1;
-            schur_useful_ += 2048.0 * nu * (nu + 1) / 2 + 512.0 * nu;
-          }
-          nc += sspan(k++);
-        }
-        B.p1 = k;
-        B.c1 = B.c0 + nc;
-        cnext += nc;
-        sbatch.push_back(B);
-      }
-      sg.bt1 = (int)sbatch.size();
-      segs.push_back(sg);
-      i = j;
-    }
-    SG_REQUIRE(cnext == ncell, SG_EINVAL, "Schur cells out of step with the batches");
-  }
-  nseg_ = (int)segs.size();
-  nwide_ = (int)wsegs.size();
-  if (pairs_flat.empty()) pairs_flat.assign(2, 0);
+  PlanSchur(ord, ncu_, &wl);
   lap("segments");
-  // deterministic reduction lists: for every camera block, the slab offsets of the chunk partials that cover
-  // it (fixed chunk order), and of the segments' rhs partials
-  std::vector<int32_t> cam_loff(NB_ + 1, 0), cam_lidx, r_loff(NB_ + 1, 0), r_lidx;
-  {
-    std::vector<std::vector<int32_t>> cl(NB_), rl(NB_);
-    for (const LinChunk& ch : lchunks) {
-      if (ch.wide || ch.nb == 0) continue;
-      for (int i = 0; i < ch.nb; ++i) cl[ch.b_lo + i].push_back(ch.cam_off + i * kCamV);
-    }
-    for (const SchurSeg& sg : segs) {   // rhs partial of block I: window columns 6 I - 16 t0 ..
-      const int ntile = sg.ntw * (sg.ntw + 1) / 2;
-      for (int i = 0; i < sg.nb; ++i)
-        rl[sg.b_lo + i].push_back(sg.s_off + 256 * ntile + 6 * (sg.b_lo + i) - 16 * sg.t0);
-    }
-    size_t rmax = 0;
-    for (int b = 0; b < NB_; ++b) rmax = std::max(rmax, rl[b].size());
-    r_lstride_ = (int)std::max<size_t>(256, (rmax + 255) / 256 * 256);   // rows padded (k_S_reduce's unbounded reads)
-    r_lidx.assign((size_t)std::max(NB_, 1) * r_lstride_, 0);
-    for (int b = 0; b < NB_; ++b) {
-      cam_loff[b + 1] = cam_loff[b] + (int)cl[b].size();
-      cam_lidx.insert(cam_lidx.end(), cl[b].begin(), cl[b].end());
-      r_loff[b] = (int)rl[b].size();
-      std::copy(rl[b].begin(), rl[b].end(), r_lidx.begin() + (size_t)b * r_lstride_);
-    }
-    if (cam_lidx.empty()) cam_lidx.push_back(0);
-  }
+  PlanReduceLists(ord, &wl);
   lap("reduce-lists");
-  // FrameDistance
-  std::vector<int32_t> fd_a(p.dist_frame, p.dist_frame + D_), fd_b(p.dist_prev, p.dist_prev + D_);
-  std::vector<int32_t> fd_boff(NB_ + 1, 0), fd_bidx;
-  {
-    std::vector<std::vector<int32_t>> lists(NB_);
-    for (int dd = 0; dd < D_; ++dd) {
-      const int ba = frame_block[fd_a[dd]], bb = frame_block[fd_b[dd]];
-      if (ba >= 0) lists[ba].push_back(2 * dd);
-      if (bb >= 0) lists[bb].push_back(2 * dd + 1);
-    }
-    for (int b = 0; b < NB_; ++b) {
-      fd_boff[b + 1] = fd_boff[b] + (int)lists[b].size();
-      fd_bidx.insert(fd_bidx.end(), lists[b].begin(), lists[b].end());
-    }
-  }
+  PlanFrameDistance(p, ord, &wl);
+  PlanIntrLists(ord, &wl);
   lap("fd");
-  // Cholesky panel envelopes: block column J's first nonzero block row lo(J)
-  std::vector<int32_t> lo_blk(NB_);
-  for (int b = 0; b < NB_; ++b) lo_blk[b] = b;
-  {
-    // exact envelope from the observations of each free point (pairs of blocks it couples)
-    for (int i = 0; i < P_; ++i) {
-      const int pt = point_perm_[i];
-      if (pfirst[pt] >= NB_) continue;
-      if (!p.point_free[pt]) continue;
-      const int lo = pfirst[pt];
-      for (int o = poff[i]; o < poff[i + 1]; ++o) {
-        const int b = frame_block[obs_frame[o]];
-        if (b >= 0) lo_blk[b] = std::min(lo_blk[b], lo);
-      }
-    }
-    for (int dd = 0; dd < D_; ++dd) {
-      const int ba = frame_block[fd_a[dd]], bb = frame_block[fd_b[dd]];
-      if (ba >= 0 && bb >= 0) {
-        const int hi3 = std::max(ba, bb), lo3 = std::min(ba, bb);
-        lo_blk[hi3] = std::min(lo_blk[hi3], lo3);
-      }
-    }
-  }
+  PlanLoBlk(ord, &wl);
   // Landmark shards: S is summed over every rank's points, so each rank must factor it with the envelope of
   // the whole problem (the union of the shards' envelopes), not of its own points.  One max all-reduce of
   // -lo(J) at load time.
   if (comm_ && (comm_->nranks() > 1 || comm_force_) && NB_ > 0) {
     std::vector<double> neg(NB_);
-    for (int b = 0; b < NB_; ++b) neg[b] = -(double)lo_blk[b];
+    for (int b = 0; b < NB_; ++b) neg[b] = -(double)wl.lo_blk[b];
     DBuf<double> env;
     env.Upload(neg, stream_);
     comm_->AllReduceMax(env.ptr, (size_t)NB_, stream_);
     SG_HIP_CHECK(hipMemcpyAsync(neg.data(), env.ptr, NB_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     SG_HIP_CHECK(hipStreamSynchronize(stream_));
-    for (int b = 0; b < NB_; ++b) lo_blk[b] = (int)(-neg[b]);
+    for (int b = 0; b < NB_; ++b) wl.lo_blk[b] = (int)(-neg[b]);
   }
-  const int npanel = (n_ + kCholNb - 1) / kCholNb;
-  std::vector<int32_t> panel_jmax(std::max(npanel, 1), 0), panel_bend(std::max(npanel, 1), 0);
-  for (int pk = 0; pk < npanel; ++pk) {
-    const int row_hi = std::min(n_, (pk + 1) * kCholNb) - 1;   // last row of the panel
-    const int blk_hi = row_hi / 6;
-    int jmax = (pk + 1) * kCholNb;
-    // columns j whose envelope starts at or before the panel's last row block
-    for (int b = 0; b < NB_; ++b)
-      if (lo_blk[b] <= blk_hi) jmax = std::max(jmax, 6 * b + 6);
-    jmax = std::min(jmax, n_);
-    panel_jmax[pk] = std::min(n_, (jmax + kCholNb - 1) / kCholNb * kCholNb);   // band end, 16-aligned
-    if (nk_) {   // the intrinsics columns couple every frame: S is dense (k_cholesky_global: arrowhead)
-      panel_bend[pk] = std::min(jmax, 6 * NB_);
-      panel_jmax[pk] = n_;
-    }
-  }
-  if (nk_) panel_jmax.insert(panel_jmax.end(), panel_bend.begin(), panel_bend.end());   // work_i_ tail
-  {
-    std::vector<int32_t> off(npanel + 1, 0);
-    for (int pk = 0; pk < npanel; ++pk)
-      off[pk + 1] = off[pk] + std::min(kCholNb, n_ - pk * kCholNb) * (panel_jmax[pk] - pk * kCholNb);
-    npack_ = (size_t)off[npanel] + n_;
-    stager_->Add(pack_off_, off);
-    // + the merged exchange's tail (k_cam_finalize modes 1, 2)
-    ntail_ = 2 * (size_t)6 * NB_ + kXNum + nranks() + 1;
-    Spk_.Resize(npack_ + ntail_);
-  }
-  // k_cholesky_global stages each panel's rows in LDS when x and 16 rows of S fit
-  // (SG_CHOL_GSTAGE=0: never, so tests reach the unstaged instance at any size)
-  chol_gstage_ = (size_t)std::max(n_, 1) * 8 * (1 + kCholNb) <= gchol_lds_max_ &&
-                 !(getenv("SG_CHOL_GSTAGE") && atoi(getenv("SG_CHOL_GSTAGE")) == 0);
-  chol_window_ = npanel <= kJendSh;   // band ends cached in LDS
-  for (int pk = 0; pk < npanel; ++pk)
-    if (panel_jmax[pk] - pk * kCholNb > kCholWS) chol_window_ = false;
-  band_tiles_ = 0;
-  for (int pk = 0; pk < npanel; ++pk)
-    band_tiles_ = std::max(band_tiles_, (panel_jmax[pk] + kCholNb - 1) / kCholNb - pk);
-  // tiled band Cholesky: every tile row's band within kTB tiles, x and z' of the whole system in LDS
-  chol_tiles_ = n_ > 0 && nk_ == 0 && npanel <= kTileMaxNT && !getenv("SG_CHOL_WINDOW");
-  for (int pk = 0; pk < npanel; ++pk)
-    if ((panel_jmax[pk] + kCholNb - 1) / kCholNb - pk > kTB) chol_tiles_ = false;
-  // free intrinsics (one 16-wide border tile): the frame band on k_chol_tiles, the border by k_chol_border
-  // (SG_CHOL_BORDER=0: the arrowhead k_cholesky_global)
-  chol_border_ = false;
-  if (nk_ > 0 && NB_ > 0 && n_ - 6 * NB_ <= kCholNb && !getenv("SG_CHOL_WINDOW") &&
-      !(getenv("SG_CHOL_BORDER") && atoi(getenv("SG_CHOL_BORDER")) == 0)) {
-    const int ntf = (6 * NB_ + kCholNb - 1) / kCholNb;
-    chol_border_ = ntf <= kTileMaxNT;
-    for (int pk = 0; pk < ntf; ++pk)
-      if ((panel_bend[pk] + kCholNb - 1) / kCholNb - pk > kTB) chol_border_ = false;
-    if (chol_border_) {
-      chol_tiles_ = true;
-      // q_K tiles and the candidate operands in LDS where they fit (else global q_K / chol_candidates)
-      border_flags_ = 0;
-      for (int f : {1, 2, 3})   // the last that fits: both, else the candidate operands, else the q_K tiles
-        if (border_lds_doubles(ntf, f, F_, D_, n_) * sizeof(double) <= border_lds_max_ &&
-            (!(f & 2) || (F_ <= kCandMax && D_ <= kCandMax)))
-          border_flags_ = f;
-    }
-  }
-  // dissected band: a second workgroup factors the bottom nd tile rows (reversed) while the first factors
-  // the top rows [0, m), both meeting at a separator of ns <= 7 tile rows (k_chol_tiles); worth it from about 12
-  // tile rows.  The separator must hold every band of the top part: ns(m) = max_{K<m} tend[K] - m.  The chain is
-  // priced in phases as max(m, nd + h) + ns, h = 2.5 phases for the bottom's hand-off (round-2 stamps: nd = 3 / 4 /
-  // 5 at ns = 7 took 198 / 188 / 193 k cycles at C2), and the cheapest m is taken (C2, whose rows are 6-7 tiles
-  // wide: m = 7, ns = 5, nd = 6 — 12 phases on the top chain instead of 14; C5, 8 tiles: ns = 7, nd = 33 as before).
-  // SG_CHOL_SEP=7: the fixed 7-row separator (tests).
-  chol_nd_ = 0;
-  chol_ns_ = kTB - 1;
-  if (chol_tiles_ && !chol_border_ && npanel >= kSplitMinNT &&
-      !(getenv("SG_CHOL_SPLIT") && atoi(getenv("SG_CHOL_SPLIT")) == 0)) {
-    const bool fixed7 = getenv("SG_CHOL_SEP") && atoi(getenv("SG_CHOL_SEP")) == kTB - 1;
-    double best = 1e30;
-    int reach = 0;   // max_{K<m} tend[K]
-    for (int m = 1; m < npanel; ++m) {
-      reach = std::max(reach, std::min(npanel, (panel_jmax[m - 1] + kCholNb - 1) / kCholNb));
-      const int ns = fixed7 ? kTB - 1 : reach - m;
-      const int nd = npanel - m - ns;
-      if (ns < 1 || ns > kTB - 1 || reach - m > ns || nd < 2) continue;
-      const double cost = std::max((double)m, nd + 2.5) + ns;
-      if (cost < best) {
-        best = cost;
-        chol_nd_ = nd;
-        chol_ns_ = ns;
-      }
-    }
-  }
-  if (chol_tiles_) {
-    // W tiles of the top and bottom halves, the bottom's z' (+ failure slot), the separator contribution
-    // and its rhs, then the constants {0, 1}
-    // (zeroed and its constants set on the device by ResetState: no host fill, no staged zeros)
-    Wg_.Resize((size_t)2 * npanel * kTB * 256 + 16 * (size_t)npanel + 49 * 256 + 7 * 16 + 2);
-    stager_->Add(tflag_, std::vector<int32_t>(2, 0));
-    tile_lds_ = (size_t)npanel * 32 * sizeof(double) + (size_t)(3 * npanel + 1) / 2 * sizeof(double);
-    chol_cand_lds_ = !chol_border_ && F_ <= kCandMax && D_ <= kCandMax &&
-                     tile_lds_ + cand_lds_bytes(F_, D_, n_) <= 100 * 1024 &&
-                     tile_lds_ + cand_lds_bytes(F_, D_, n_) <= tile_lds_set_;
-    if (chol_cand_lds_) tile_lds_ += cand_lds_bytes(F_, D_, n_);
-    if (tile_lds_ > tile_lds_set_) {   // beyond the LDS granted at construction: the one-workgroup kernels
-      chol_tiles_ = false;
-      chol_border_ = false;
-      chol_nd_ = 0;
-    }
-  }
-  // k_S_reduce work: the band tiles (R <= C) of the frame columns, and per tile the segment tiles covering it
-  // (segment order).  A segment tile outside the band is zero (no point couples its rows and columns).
-  std::vector<int32_t> stile, s_loff, s_lidx;
-  {
-    const int nft = (6 * NB_ + kCholNb - 1) / kCholNb;
-    std::vector<int32_t> row_off(nft + 1, 0), cend(nft, 0);
-    for (int R = 0; R < nft; ++R) {
-      cend[R] = std::min(nft, (panel_jmax[R] + kCholNb - 1) / kCholNb);
-      row_off[R + 1] = row_off[R] + std::max(0, cend[R] - R);
-      for (int C = R; C < cend[R]; ++C) stile.push_back((R << 16) | C);
-    }
-    std::vector<std::vector<int32_t>> tl(stile.size());
-    for (const SchurSeg& sg : segs)
-      for (int u = 0; u < sg.ntw * (sg.ntw + 1) / 2; ++u) {
-        const int R = sg.t0 + schur_tile_r(u), C = sg.t0 + schur_tile_c(u);
-        if (R < nft && C < cend[R]) tl[row_off[R] + C - R].push_back(sg.s_off + 256 * u);
-      }
-    size_t smax = 0;
-    for (const auto& l : tl) smax = std::max(smax, l.size());
-    s_lstride_ = (int)std::max<size_t>(256, (smax + 255) / 256 * 256);   // rows padded (k_S_reduce's unbounded reads)
-    s_lidx.assign(std::max<size_t>(tl.size(), 1) * s_lstride_, 0);
-    for (size_t t = 0; t < tl.size(); ++t) {
-      s_loff.push_back((int)tl[t].size());
-      std::copy(tl[t].begin(), tl[t].end(), s_lidx.begin() + t * s_lstride_);
-    }
-    nstile_ = (int)stile.size();
-    if (stile.empty()) stile.push_back(0);
-    if (s_loff.empty()) s_loff.push_back(0);
-  }
+  const Envelope env = PlanEnvelope(ord, wl.lo_blk, wl.segs, wl.nseg);
+  chol_ = PlanChol(ord, env, CholGrants{tile_lds_set_, gchol_lds_max_, border_lds_max_}, knobs);
+  wk_ = wl;    // (the counts: the lists live on the device only)
+  env_ = env;
   lap("envelope");
-  // upload batch 2 — the work lists: one pinned staging copy and one scatter launch (stager.h)
-  stg.Add(lchunks_d_, lchunks);
-  stg.Add(lrounds_d_, lrounds);
-  stg.Add(segs_, segs.empty() ? std::vector<SchurSeg>(1) : segs);
-  stg.Add(sbatch_, sbatch.empty() ? std::vector<SchurBatch>(1) : sbatch);
-  stg.Add(wsegs_, wsegs.empty() ? std::vector<WideSeg>(1) : wsegs);
-  stg.Add(pinfo_, pinfo);
-  stg.Add(pmx_, pmx);
-  stg.Add(cells_, cells);
-  stg.Add(cell_obs_, cell_obs);
-  stg.Add(stile_, stile);
-  stg.Add(pairs_, pairs_flat);
-  seg_fail_.Resize(std::max(nseg_ + nwide_, 1));
-  stg.Add(cam_loff_, cam_loff);
-  stg.Add(cam_lidx_, cam_lidx);
-  stg.Add(s_loff_, s_loff);
-  stg.Add(s_lidx_, s_lidx);
-  stg.Add(r_loff_, r_loff);
-  stg.Add(r_lidx_, r_lidx);
-  // padded to one entry: k_cam_finalize prefetches fd_a[0] / fd_b[0] beside LmState even when D = 0
-  stg.Add(fd_a_, fd_a.empty() ? std::vector<int32_t>{0} : fd_a);
-  stg.Add(fd_b_, fd_b.empty() ? std::vector<int32_t>{0} : fd_b);
-  stg.Add(fd_boff_, fd_boff);
-  stg.Add(fd_bidx_, fd_bidx.empty() ? std::vector<int32_t>{0} : fd_bidx);
-  stg.Add(work_i_, panel_jmax);
-  {
-    // FrameDistance cross-block lookup for the on-the-fly assembly: fd_pair[I*NB+J] (I<J) = 2 * residual +
-    // (1 if the residual's frame a is block J, not I), so k_S_reduce reads the orientation with the index
-    // instead of two more dependent loads (fd_a, frame_block)
-    std::vector<int32_t> fd_pair((size_t)std::max(NB_, 1) * std::max(NB_, 1), -1);
-    for (int dd = 0; dd < D_; ++dd) {
-      const int ba = frame_block[fd_a[dd]], bb = frame_block[fd_b[dd]];
-      if (ba >= 0 && bb >= 0 && ba != bb)
-        fd_pair[(size_t)std::min(ba, bb) * NB_ + std::max(ba, bb)] = 2 * dd + (ba < bb ? 0 : 1);
-    }
-    stg.Add(fd_pair_, fd_pair);
-    rdg_.Resize((size_t)std::max(n_, 1) + kCholNb);   // + padding rows of the last panel
+  stg.Add(pack_off_, env.pack_off);
+  // + the merged exchange's tail (k_cam_finalize modes 1, 2)
+  ntail_ = 2 * (size_t)6 * NB_ + kXNum + nranks() + 1;
+  Spk_.Resize(env.npack + ntail_);
+  if (chol_.wg_size) {   // (zeroed and its constants set on the device by ResetState: no host fill, no staged zeros)
+    Wg_.Resize(chol_.wg_size);
+    stg.Add(tflag_, std::vector<int32_t>(2, 0));
   }
+  // upload batch 2 — the work lists: one pinned staging copy and one scatter launch (stager.h)
+  stg.Add(lchunks_d_, wl.lchunks);
+  stg.Add(lrounds_d_, wl.lrounds);
+  stg.Add(segs_, wl.segs);
+  stg.Add(sbatch_, wl.sbatch);
+  stg.Add(wsegs_, wl.wsegs);
+  stg.Add(pinfo_, wl.pinfo);
+  stg.Add(pmx_, wl.pmx);
+  stg.Add(cells_, wl.cells);
+  stg.Add(cell_obs_, wl.cell_obs);
+  stg.Add(stile_, env.stile);
+  stg.Add(pairs_, wl.pairs);
+  seg_fail_.Resize(std::max(wl.nseg + wl.nwide, 1));
+  stg.Add(cam_loff_, wl.cam_loff);
+  stg.Add(cam_lidx_, wl.cam_lidx);
+  stg.Add(s_loff_, env.s_loff);
+  stg.Add(s_lidx_, env.s_lidx);
+  stg.Add(r_loff_, wl.r_loff);
+  stg.Add(r_lidx_, wl.r_lidx);
+  stg.Add(fd_a_, wl.fd_a);
+  stg.Add(fd_b_, wl.fd_b);
+  stg.Add(fd_boff_, wl.fd_boff);
+  stg.Add(fd_bidx_, wl.fd_bidx);
+  stg.Add(work_i_, env.panel_jmax);
+  stg.Add(fd_pair_, wl.fd_pair);
+  rdg_.Resize((size_t)std::max(n_, 1) + kCholNb);   // + padding rows of the last panel
   // the linearization's buffers hold two slots (current point, k_update_lin's candidate)
   jslot_ = (size_t)((std::max(M_, 1) + 63) & ~63) * kJStride;   // whole 64-observation blocks (jidx2)
   J_.Resize(2 * jslot_);
@@ -900,35 +386,18 @@ void BaSolver::Load(const sg_problem& p) {
   diag_c_.Resize(nn);
   camdiag_.Resize(nn);
   camg_.Resize(nn);
-  cslot_ = std::max(lcam_off, 1);
+  cslot_ = std::max(wl.lcam_off, 1);
   cam_slab_.Resize(2 * cslot_);
-  lin_scal_.Resize(2 * (size_t)std::max(nlin_, 1) * kNScal);
-  S_slab_.Resize(std::max(s_off, 1));
-  chunk_scal_.Resize((size_t)std::max(npu_, 1) * kNScal);
-  stg.Add(pu_units_, pu_units);
+  lin_scal_.Resize(2 * (size_t)std::max(wl.nlin, 1) * kNScal);
+  S_slab_.Resize(std::max(wl.s_off, 1));
+  chunk_scal_.Resize((size_t)std::max(wl.npu, 1) * kNScal);
+  stg.Add(pu_units_, wl.pu_units);
   if (nk_) {
-    // free intrinsics: each frame block's non-fixed observations (block NB: the fixed frames'), for k_intr_fk
-    std::vector<int32_t> boff(NB_ + 2, 0), bidx;
-    for (int o = 0; o < M_; ++o)
-      if (!(obs_meta[o] & kMetaFixed)) {
-        const int b = meta_block(obs_meta[o]);
-        boff[(b >= 0 ? b : NB_) + 1] += 1;
-      }
-    for (int b = 0; b <= NB_; ++b) boff[b + 1] += boff[b];
-    bidx.resize(std::max(boff[NB_ + 1], 1), 0);
-    std::vector<int32_t> fill(boff.begin(), boff.end() - 1);
-    for (int o = 0; o < M_; ++o)
-      if (!(obs_meta[o] & kMetaFixed)) {
-        const int b = meta_block(obs_meta[o]);
-        bidx[fill[b >= 0 ? b : NB_]++] = o;
-      }
-    stg.Add(intr_boff_, boff);
-    stg.Add(intr_bidx_, bidx);
-    // slices per block list: about one observation per thread of a k_intr_fk workgroup
-    int lmax = 1;
-    for (int b = 0; b <= NB_; ++b) lmax = std::max(lmax, boff[b + 1] - boff[b]);
-    intr_nsl_ = std::max(1, std::min(32, (lmax + 255) / 256));
+    stg.Add(intr_boff_, wl.intr_boff);
+    stg.Add(intr_bidx_, wl.intr_bidx);
   }
+  point_perm_ = std::move(ord.point_perm);
+  obs_perm_ = std::move(ord.obs_perm);
   if (host_timing) DevMark(s, 1);
   stg.Flush(s);
   if (host_timing) DevMark(s, 2);
@@ -953,7 +422,7 @@ void BaSolver::Load(const sg_problem& p) {
     Yk_.Resize(28 * (size_t)std::max(P_, 1) * ncam_);
     kpart_.Resize((size_t)(NB_ + 1) * ncam_ * 42);
   }
-  stamp_on_ = getenv("SG_STAMP") && getenv("SG_STAMP")[0] == '1';
+  stamp_on_ = knobs.stamp;
   if (stamp_on_) stamps_.Resize(kSegStamp + 8 * kSegStampMax);
   lap("resize");
   ResetState(s);
@@ -961,31 +430,7 @@ void BaSolver::Load(const sg_problem& p) {
   lap("reset");
   WaitStream(s);
   lap("uploads");
-  if (host_timing) {
-    float a = 0, b = 0, c = 0;
-    (void)hipEventElapsedTime(&a, dev_marks_[0], dev_marks_[1]);
-    (void)hipEventElapsedTime(&b, dev_marks_[1], dev_marks_[2]);
-    (void)hipEventElapsedTime(&c, dev_marks_[2], dev_marks_[3]);
-    float e = 0;
-    (void)hipEventElapsedTime(&e, dev_marks_[4], dev_marks_[3]);
-    const double hw = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - load_t0).count();
-    char buf[320];
-    snprintf(buf, sizeof(buf), " [device: batch1..batch2 %.2f, scatter2 %.2f, reset %.2f; load start..reset: device "
-             "%.2f, host %.2f]", a, b, c, e, hw);
-    lap_log += buf;
-    if (idle_valid_prev) {
-      float g = 0;
-      const hipError_t ge = hipEventElapsedTime(&g, ev_idle_prev_, dev_marks_[4]);
-      snprintf(buf, sizeof(buf), " [last idle..load start: device %.2f (%d), host %.2f]", g, (int)ge, idle_gap_host);
-      lap_log += buf;
-    }
-  }
-  if (host_timing) {
-    char buf[96];
-    snprintf(buf, sizeof(buf), " (staged %.2f MB; device allocations so far %ld)", stg.staged_bytes() / 1e6,
-             g_dbuf_allocs.load());
-    lap_log += buf;
-  }
+  if (host_timing) lap_log += LoadDeviceTimes(load_t0, idle_valid_prev, idle_gap_host);
   SaveStructure(p);
   full_loads_++;
   if (host_timing) {
@@ -1113,7 +558,7 @@ void BaSolver::ResetState(hipStream_t s) {
   put(6, chunk_scal_.ptr, chunk_scal_.size * sizeof(double));
   put(7, S_.ptr, (S_.size - 2) * sizeof(double));
   z.c01[0] = S_.ptr + S_.size - 2;   // k_chol_tiles: padding entries of the last tile
-  if (chol_tiles_ && Wg_.size >= 2) {   // its W tiles, z', separator terms, then its own {0, 1}
+  if (chol_.tiles && Wg_.size >= 2) {   // its W tiles, z', separator terms, then its own {0, 1}
     put(8, Wg_.ptr, (Wg_.size - 2) * sizeof(double));
     z.c01[1] = Wg_.ptr + Wg_.size - 2;
   }
@@ -1220,7 +665,7 @@ Dev BaSolver::MakeDev() {
       d.g[sl] = g_.ptr + sl * 4 * pp;
       d.cam_slab[sl] = cam_slab_.ptr + sl * cslot_;
       d.cam_wide[sl] = cam_wide_.ptr + sl * (size_t)std::max(NB_, 1) * kCamV;
-      d.lin_scal[sl] = lin_scal_.ptr + sl * (size_t)std::max(nlin_, 1) * kNScal;
+      d.lin_scal[sl] = lin_scal_.ptr + sl * (size_t)std::max(wk_.nlin, 1) * kNScal;
     }
   }
   d.spec = spec_ ? 1 : 0;
@@ -1238,8 +683,8 @@ Dev BaSolver::MakeDev() {
   d.s_lidx = s_lidx_.ptr;
   d.r_loff = r_loff_.ptr;
   d.r_lidx = r_lidx_.ptr;
-  d.s_lstride = s_lstride_;
-  d.r_lstride = r_lstride_;
+  d.s_lstride = env_.s_lstride;
+  d.r_lstride = wk_.r_lstride;
   d.S_slab = S_slab_.ptr;
   d.chunk_scal = chunk_scal_.ptr;
   d.S_wide = S_wide_.ptr;
@@ -1247,7 +692,7 @@ Dev BaSolver::MakeDev() {
   d.xchg_cam = xchg_cam_.ptr;
   d.xcam_loc = xchg_cam_.ptr + (size_t)NB_ * kCamV + kXNum + nranks();
   d.xchg_cand = xchg_cam_.ptr + 2 * ((size_t)NB_ * kCamV + kXNum + nranks());
-  d.xtail = Spk_.ptr + npack_;
+  d.xtail = Spk_.ptr + env_.npack;
   d.rank = comm_ ? comm_->rank() : 0;
   d.nranks = nranks();
   d.S = S_.ptr;
@@ -1261,20 +706,20 @@ Dev BaSolver::MakeDev() {
   d.obs_pnt = obs_pnt_.ptr;
   d.lchunks = lchunks_d_.ptr;
   d.lrounds = lrounds_d_.ptr;
-  d.nlin = nlin_;
-  d.npu = npu_;
+  d.nlin = wk_.nlin;
+  d.npu = wk_.npu;
   d.pu_units = pu_units_.ptr;
   d.segs = segs_.ptr;
-  d.nseg = nseg_;
+  d.nseg = wk_.nseg;
   d.sbatch = sbatch_.ptr;
   d.pinfo = reinterpret_cast<const int2*>(pinfo_.ptr);
   d.pmx = reinterpret_cast<const int4*>(pmx_.ptr);
   d.cells = reinterpret_cast<const int4*>(cells_.ptr);
   d.cell_obs = cell_obs_.ptr;
   d.wsegs = wsegs_.ptr;
-  d.nwide = nwide_;
+  d.nwide = wk_.nwide;
   d.stile = stile_.ptr;
-  d.nstile = nstile_;
+  d.nstile = env_.nstile;
   d.seg_fail = seg_fail_.ptr;
   d.pairs = reinterpret_cast<const int2*>(pairs_.ptr);
   d.assemble = (!comm_ || comm_->rank() == 0) ? 1 : 0;
@@ -1490,7 +935,7 @@ void BaSolver::EnqueueIterations(int n) {
     }
     if (!merged) AllReduceSum(xchg_cam_.ptr, (size_t)nv + kXNum + nranks());
     if (nk_) {
-      LaunchIntrLinearizeK(stream_, d, n_, nk_, NB_, ncam_, M_, intr_nsl_);
+      LaunchIntrLinearizeK(stream_, d, n_, nk_, NB_, ncam_, M_, wk_.intr_nsl);
     }
     if (!fin_in_schur && !fin1_in_schur) {
       TimedLaunchBegin(kKCamFinal);
@@ -1498,18 +943,18 @@ void BaSolver::EnqueueIterations(int n) {
       TimedLaunchEnd(kKCamFinal);
     }
     TimedLaunchBegin(kKSchur);
-    LaunchSchurK(std::max(nseg_, 1), nwide_, fin_in_schur ? 1 : (fin1_in_schur ? 2 : 0), stream_, d);
+    LaunchSchurK(std::max(wk_.nseg, 1), wk_.nwide, fin_in_schur ? 1 : (fin1_in_schur ? 2 : 0), stream_, d);
     TimedLaunchEnd(kKSchur);
     TimedLaunchBegin(kKSReduce);
-    const int nwv = nstile_ + NB_;
+    const int nwv = env_.nstile + NB_;
     // S is final after k_S_reduce (one rank, no free intrinsics, no merged damping; a forced pack / unpack on one
     // rank is a copy): it also factors the first diagonal tile for k_chol_tiles (flags bit 4)
     const int samode = merged ? 2 : (d.assemble ? 1 : 0);
-    const bool zpre = chol_tiles_ && !chol_border_ && nk_ == 0 && samode == 1 && !(multi_x || merged) && !chol_zpre_off_;
+    const bool zpre = chol_.tiles && !chol_.border && nk_ == 0 && samode == 1 && !(multi_x || merged) && !chol_zpre_off_;
     LaunchSReduceK(std::max(nwv, 1), stream_, d, samode, zpre ? 1 : 0);
     TimedLaunchEnd(kKSReduce);
     if (nk_) {
-      LaunchIntrSchurK(stream_, d, n_, nk_, NB_, ncam_, P_, intr_nsl_);
+      LaunchIntrSchurK(stream_, d, n_, nk_, NB_, ncam_, P_, wk_.intr_nsl);
     }
     if (multi_x || pack_force_ || merged) {
       // the band of S and the rhs partial are summed over landmark shards (packed: the band only), with the
@@ -1519,7 +964,7 @@ void BaSolver::EnqueueIterations(int n) {
       TimedLaunchBegin(kKXchg);   // pack, all-reduce, unpack
       LaunchSPackK(pg, stream_, S_.ptr, n_, (const int32_t*)work_i_.ptr, (const int32_t*)pack_off_.ptr, npanel,
                    Spk_.ptr, 0);
-      AllReduceSum(Spk_.ptr, npack_ + (merged ? ntail_ : 0));
+      AllReduceSum(Spk_.ptr, env_.npack + (merged ? ntail_ : 0));
       if (fin1_in_schur)
         LaunchSUnpackFinK(pg, stream_, d, (const int32_t*)work_i_.ptr, (const int32_t*)pack_off_.ptr, npanel,
                           Spk_.ptr);
@@ -1534,13 +979,13 @@ void BaSolver::EnqueueIterations(int n) {
       }
     }
     TimedLaunchBegin(kKChol);
-    if (chol_tiles_)
-      LaunchCholTiles(d.stamps != nullptr, dim3(chol_nd_ > 0 ? 2 : 1), d,
-                      (chol_cand_lds_ ? 2 : 0) | (chol_force_tmo_ ? 4 : 0) | (zpre ? 16 : 0));
-    else if (chol_window_)
+    if (chol_.tiles)
+      LaunchCholTiles(d.stamps != nullptr, dim3(chol_.nd > 0 ? 2 : 1), d,
+                      (chol_.cand_lds ? 2 : 0) | (chol_force_tmo_ ? 4 : 0) | (zpre ? 16 : 0));
+    else if (chol_.window)
       LaunchCholWindowK(d.stamps != nullptr, stream_, d, (const int32_t*)work_i_.ptr, rdg_.ptr);
     else
-      LaunchCholGlobalK(chol_gstage_, (size_t)std::max(n_, 1) * 8 * (chol_gstage_ ? 1 + kCholNb : 1), stream_, d,
+      LaunchCholGlobalK(chol_.gstage, (size_t)std::max(n_, 1) * 8 * (chol_.gstage ? 1 + kCholNb : 1), stream_, d,
                         (const int32_t*)work_i_.ptr, rdg_.ptr);
     TimedLaunchEnd(kKChol);
     if (nk_) LaunchIntrStepK(stream_, d);
@@ -1548,7 +993,7 @@ void BaSolver::EnqueueIterations(int n) {
     if (spec_) {
       LaunchUpdateLin(d);
     } else {
-      LaunchPointUpdateK(std::max(npu_, 1), stream_, d);
+      LaunchPointUpdateK(std::max(wk_.npu, 1), stream_, d);
     }
     TimedLaunchEnd(kKPointUpd);
     const bool multi = comm_ && comm_->nranks() > 1;
@@ -1600,10 +1045,10 @@ void BaSolver::Sweep(int n) {
   SG_HIP_CHECK(hipGetLastError());
 }
 
-void BaSolver::LaunchLinearize(const Dev& d) { LaunchLinearizeK(lin_waves_, std::max(nlin_, 1), stream_, d); }
+void BaSolver::LaunchLinearize(const Dev& d) { LaunchLinearizeK(wk_.lin_waves, std::max(wk_.nlin, 1), stream_, d); }
 
 void BaSolver::LaunchUpdateLin(const Dev& d) {
-  LaunchUpdateLinK(stamp_on_, lin_waves_, std::max(nlin_, 1), stream_, d);
+  LaunchUpdateLinK(stamp_on_, wk_.lin_waves, std::max(wk_.nlin, 1), stream_, d);
 }
 
 std::vector<unsigned long long> BaSolver::Stamps() {
@@ -1752,7 +1197,7 @@ int BaSolver::KernelWork(double* bytes, double* flops, int max) {
   // k_schur: the record less r~ (rotation pairs + J~p) and the observation meta; per point V, g, scales, X.w and
   // the written Vinv / t / diag
   by[kKSchur] = M * (jrec - 16 + 4) + P * (80 + 32 + 32 + 8 + 32 + 80 + 32);
-  fl[kKSchur] = 2048.0 * schur_mfma_ + 512.0 * schur_rhs_;   // 16x16x4 tile updates, 4x4x4 (4-block) rhs slots
+  fl[kKSchur] = 2048.0 * wk_.schur_mfma + 512.0 * wk_.schur_rhs;   // 16x16x4 tile updates, 4x4x4 (4-block) rhs slots
   by[kKPointUpd] = M * (jrec + 16 + 4) + P * (32 + 32 + 80 + 32 + 32);
   if (spec_) {   // k_update_lin: the update's traffic plus the candidate's linearization (a second J record, V, g)
     by[kKPointUpd] = M * (jrec + jrec + 16 + 4 + 4 + 4) + P * (32 + 32 + 80 + 32 + 32 + 80 + 32) + NB * kCamV * 8;
@@ -1773,7 +1218,7 @@ int BaSolver::KernelWork(double* bytes, double* flops, int max) {
   //               camera block pose 56 + U_i / g_c 8 (21 + 6)
   if (max > kKNum) {
     bytes[kKNum] = 0.0;
-    flops[kKNum] = schur_useful_;
+    flops[kKNum] = wk_.schur_useful;
     ++k;
   }
   if (max > kKNum + 1) {
@@ -1791,15 +1236,15 @@ void BaSolver::Info(sg_ba_info* o) const {
   o->num_obs = M_;
   o->num_blocks = NB_;
   o->n = n_;
-  o->band_tiles = band_tiles_;
-  o->cholesky_path = chol_border_ ? 4 : chol_tiles_ ? 0 : (chol_window_ ? 1 : (chol_gstage_ ? 2 : 3));
-  o->cholesky_split = chol_tiles_ ? chol_nd_ : 0;
-  o->num_pairs = (int32_t)std::min<size_t>(npairs_, INT32_MAX);
+  o->band_tiles = env_.band_tiles;
+  o->cholesky_path = chol_.border ? 4 : chol_.tiles ? 0 : (chol_.window ? 1 : (chol_.gstage ? 2 : 3));
+  o->cholesky_split = chol_.tiles ? chol_.nd : 0;
+  o->num_pairs = (int32_t)std::min<size_t>(wk_.npairs, INT32_MAX);
   o->rank = comm_ ? comm_->rank() : 0;
   o->nranks = comm_ ? comm_->nranks() : 1;
   o->num_allreduces = nallreduce_;
-  o->lin_waves = lin_waves_;
-  o->cholesky_separator = chol_tiles_ && chol_nd_ > 0 ? chol_ns_ : 0;
+  o->lin_waves = wk_.lin_waves;
+  o->cholesky_separator = chol_.tiles && chol_.nd > 0 ? chol_.ns : 0;
 }
 
 double BaSolver::ReprojectMap(sg_map* m) {

@@ -15,10 +15,8 @@ namespace sg {
 typedef double f64x4 __attribute__((ext_vector_type(4)));   // v_mfma_f64_16x16x4f64 C/D operand
 #endif
 
-// Augmented slot order of a segment window: level c = 0 .. kSchurTW-1 holds the window tiles (0, c) .. (c, c),
-// then the rhs tile of tile row c (E_c^T w in its column 0).  A point whose columns end in window tile jhi
-// touches exactly the levels <= jhi: a prefix of schur_aug_base(jhi + 1) slots.  Wave W owns slots u = W + 4 s.
-__host__ __device__ constexpr int schur_aug_base(int c) { return c * (c + 3) / 2; }
+// The augmented slot order of a segment window (schur_aug_base) and the slab's tile order (schur_tile_r,
+// schur_tile_c): ba_layout.h.
 __host__ __device__ constexpr int schur_aug_c(int u) {
   int c = 0;
   while (schur_aug_base(c + 1) <= u) ++c;
@@ -27,12 +25,6 @@ __host__ __device__ constexpr int schur_aug_c(int u) {
 __host__ __device__ constexpr int schur_aug_r(int u) { return u - schur_aug_base(schur_aug_c(u)); }   // c + 1: rhs
 // window tile (r, c), r <= c, in the segment slab's column-major upper order
 __host__ __device__ constexpr int schur_tile_index(int r, int c) { return c * (c + 1) / 2 + r; }
-__host__ __device__ constexpr int schur_tile_c(int t) {
-  int c = 0;
-  while ((c + 1) * (c + 2) / 2 <= t) ++c;
-  return c;
-}
-__host__ __device__ constexpr int schur_tile_r(int t) { return t - schur_tile_c(t) * (schur_tile_c(t) + 1) / 2; }
 // operand columns wave W reads
 __host__ __device__ constexpr unsigned schur_need(int W) {
   unsigned m = 0;
