@@ -280,6 +280,27 @@ int sg_slam_load_counts(const sg_slam* s, int32_t* full_loads, int32_t* value_lo
  * A development aid for sizing the host share of a real call (tools/e2e_replay.py). */
 int sg_slam_last_phase_ms(const sg_slam* s, double* ms4);
 int sg_slam_last_summary(const sg_slam* s, sg_solver_summary* out);
+/* Pose-only (motion-only) bundle adjustment: given the landmarks as they are, where are these frames?  It fills
+ * the place of Slam::SolveFramePose (slam.h:21-65; the reference disabled its body, slam.cpp:180-182, and calls it
+ * as Matcher::Track's update_frames hook, main.cpp:560-563).  For each listed frame f, solved on its own against
+ * the map as it is at entry, the problem Slam::SetupProblem (slam.cpp:257-414) would build if only f were free:
+ * one ReprojectionError with CauchyLoss(range) per observation of f that is not disabled and whose point is
+ * slam-usable (slam.cpp:280-283); q_f free with ceres::QuaternionParameterization (slam.cpp:312-313), t_f free,
+ * every point and the intrinsics constant; with_frame_distance and frame_prev[f] >= 0 add FrameDistance(150) with
+ * CauchyLoss(15) to the previous frame's constant translation (slam.cpp:86-105, 401-410).  The solver is the
+ * handle's sg_solver_options (sg_slam_set_options) on the Ceres 1.8 LM of sg_ba_solve; all frames of a call run in
+ * one device launch, one workgroup each.
+ *   - A frame with fewer than 3 usable observations is not solved: solved[i] = 0, SG_DID_NOT_RUN, pose untouched.
+ *   - A frame whose solve ends with ok = 0 (a start behind the camera: SG_NUMERICAL_FAILURE) also keeps its pose
+ *     and gets solved[i] = 0.  Otherwise q_f and t_f are written into the map; nothing else of the map is.
+ *   - A frame index out of range or listed twice: SG_EINVAL, nothing changed.  n == 0 returns SG_OK before the
+ *     handle or the device is touched.
+ * summaries (may be NULL) receives each frame's summary.  As Slam::Run does for any solve (slam.cpp:517-518),
+ * sg_slam_iterations grows by the num_iterations of the frames that ran, and sg_slam_error / sg_slam_last_summary
+ * take the values of the last listed frame that ran.  No communicator is involved: rank-local on a sharded handle. */
+int sg_slam_solve_frame_poses(sg_slam* s, sg_map* map, const int32_t* frames, int32_t n, double range,
+                              int32_t with_frame_distance, int32_t* solved /*[n]*/,
+                              sg_solver_summary* summaries /*[n], may be NULL*/);
 
 /* ------------------------------------------------------------------------------------------------
  * Front end: HessianTracker (hessian.h:9-270) and the forward/backward matching step of Matcher

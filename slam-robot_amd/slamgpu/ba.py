@@ -255,6 +255,26 @@ class Slam:
         """slam.cpp:180-182: the reference returns false unconditionally (dead code after the return)."""
         return False
 
+    def SolveFramePoses(self, m: MapArrays, frames, range_: float, with_frame_distance: bool = False) -> list:
+        """Pose-only bundle adjustment (sg_slam_solve_frame_poses): each listed frame's pose against the map's
+        points as they are, all frames in one device launch.  Updates m.q / m.t of the solved frames in place and
+        returns one bool per listed frame; frame_pose_summaries() has their summaries."""
+        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        n = len(fr)
+        solved = np.zeros(n, dtype=np.int32)
+        sums = (SgSolverSummary * max(n, 1))()
+        ms = m.struct()
+        check(self.lib.sg_slam_solve_frame_poses(self.h, C.byref(ms), fr.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                                                 range_, int(with_frame_distance),
+                                                 solved.ctypes.data_as(C.POINTER(C.c_int32)), sums),
+              "Slam::SolveFramePoses")
+        self._pose_summaries = [sums[i].as_dict() for i in range(n)]
+        return [bool(v) for v in solved]
+
+    def frame_pose_summaries(self) -> list:
+        """Summary dicts of the last SolveFramePoses call, one per listed frame."""
+        return list(getattr(self, "_pose_summaries", []))
+
     def ReprojectMap(self, m: MapArrays) -> float:
         mean = C.c_double()
         ms = m.struct()
