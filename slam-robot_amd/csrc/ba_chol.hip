@@ -1058,10 +1058,27 @@ __device__ __forceinline__ bool tile_diag(const f64x4& D, double ypart, TileShar
   return bad;
 }
 
+// Every byte the dissected band's bottom workgroup hands to the top one in the same launch (its W tiles, z', the
+// failure slots, the separator contribution) is stored write-through, by agent-scope relaxed stores (sc1), so the
+// hand-off needs no L2 write-back: the storing waves drain their stores and one lane signals.  The separator
+// contribution and the failure slots are read by the matching loads (sc1: served past the reading CU's L1), every
+// load of them, each wave after its own poll has matched or behind a barrier that follows it: no L1 invalidate on
+// the chain.  The W tiles and z' are read only in the back substitution, by plain loads behind an agent acquire
+// that their waves run off the chain.
+__device__ __forceinline__ void st_wt(double* p, double v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ double ld_wt(const double* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // z'_K = Z_K^T z_K for the back substitution, from the posted Z_K and z_K (LDS ring slot K & 3): formed by
 // the owner one phase later (its late phase), off the pivot chain.
 // zg (bordered mode): Z_K row-major into slot 0 of W row K (W tiles start at slot 1), for k_chol_border.
-__device__ __forceinline__ void tile_zp(const TileShared& sh, double* zp, int K, int lane, double* zg = nullptr) {
+// zw (the dissected band's bottom half): z' also goes to global memory, write-through, for the top half's back
+// substitution of the bottom rows.
+__device__ __forceinline__ void tile_zp(const TileShared& sh, double* zp, int K, int lane, double* zg = nullptr,
+                                        double* zw = nullptr) {
   if (lane < 16) {
     const double* Zs = sh.Zs[K & 3];
     const double* zk = sh.zK[K & 3];
@@ -1069,6 +1086,7 @@ __device__ __forceinline__ void tile_zp(const TileShared& sh, double* zp, int K,
 #pragma unroll
     for (int r = 0; r < kCholNb; ++r) s = fma(Zs[r * kTLd + lane], zk[r], s);
     zp[16 * K + lane] = s;
+    if (zw) st_wt(zw + 16 * K + lane, s);
   }
   if (zg) {
     const double* Zs = sh.Zs[K & 3];
@@ -1102,9 +1120,21 @@ __device__ __forceinline__ void tile_zp(const TileShared& sh, double* zp, int K,
 #else
 #define SG_AST(slot) {}
 #define SG_PTRACE(K, slot)                                                                  \
-  if (kStamp && lane == 0 && (K) < kTraceK)                                                \
+  if (kStamp && lane == 0 && (K) < kTraceK - 1)                                            \
     d.stamps[64 + ((size_t)blockIdx.x * kTraceK + (K)) * 16 + (slot)] = __builtin_amdgcn_s_memtime();
 #endif
+// Separator hand-off stamps (SG_STAMP=1 builds; tools/handoff_stamps.py): the last trace row of each workgroup,
+// kept in registers until the launch's end.  Top (the wave owning column m at the poll): 0 poll arrival -> match,
+// 1 match -> sep_merge's loads landed, 2 launches.  Bottom (thread 0): 0 last phase's barrier -> tile_final and
+// sep_write issued, 1 (nothing now: once a barrier and the z' copy), 2 -> this wave's stores drained and the
+// workgroup's barrier, 3 -> the flag store, 4 launches, 5 launch start -> last phase's barrier.
+#define SG_HSTAMP(i)                                                 \
+  if (kStamp && lane == 0) {                                         \
+    const unsigned long long now_ = __builtin_amdgcn_s_memtime();   \
+    hacc[i] = now_ - hlast;                                          \
+    hlast = now_;                                                    \
+  }
+constexpr int kHoStamp = 64 + (kTraceK - 1) * 16;   // + wg kTraceK 16
 
 // W_KJ = Z_K^T U_KJ (= U_KK^-1 U_KJ) of one row-K tile, and its store to global memory for the back
 // substitution (kept apart so that loads issued in between do not reuse the stores' data registers, which
@@ -1116,10 +1146,17 @@ __device__ __forceinline__ f64x4 tile_w(const f64x4& U, const double* Zs, int li
   for (int s = 0; s < 4; ++s) zt[s] = Zs[(4 * s + lk) * kTLd + li];
   return mfma_f64_k16(zt, U, zero);
 }
-__device__ __forceinline__ void tile_w_store(const f64x4& Wt, double* __restrict__ Wg, int K, int J, int lane) {
+// wt (workgroup-uniform): the dissected band's bottom half stores its W tiles write-through.
+__device__ __forceinline__ void tile_w_store(const f64x4& Wt, double* __restrict__ Wg, int K, int J, int lane,
+                                             bool wt) {
   double* wg = Wg + ((size_t)K * kTB + (J - K)) * 256 + lane;
+  if (wt) {
 #pragma unroll
-  for (int q = 0; q < 4; ++q) wg[q * 64] = Wt[q];
+    for (int q = 0; q < 4; ++q) st_wt(wg + q * 64, Wt[q]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) wg[q * 64] = Wt[q];
+  }
 }
 
 // The accumulator slots rotate with the phase: in phase K, slot s of a wave's column J holds tile row
@@ -1160,8 +1197,9 @@ template <bool kStamp>
 __device__ __forceinline__ void tile_phase(f64x4 (&acc)[kTB], double& ypart, int& J, bool& late, bool& bad,
                                            bool& tmo, TileShared& sh, const Dev& d,
                                            double* __restrict__ Wg, double* zp, const int* tend, int K, int NT,
-                                           int lane, int li, int lk, const TileSrc& ts, double* zg,
+                                           int lane, int li, int lk, const TileSrc& ts, double* zg, double* zw,
                                            unsigned long long (&tacc)[16], unsigned long long& tlast) {
+  const bool wt = zw != nullptr;   // the dissected band's bottom half: W tiles and z' write-through
   if (late) {
 #ifdef SG_X_NOLATE   // timing-only A/B (round 6): the late wave's W tile, reload and z' skipped (results wrong)
     J += kTB;
@@ -1180,9 +1218,9 @@ __device__ __forceinline__ void tile_phase(f64x4 (&acc)[kTB], double& ypart, int
     tile_col_load(acc, ypart, d, J, K, li, lk, ts);
 #endif
     SG_AST(1)
-    if (hasw) tile_w_store(Wt, Wg, K - 1, Jw, lane);
+    if (hasw) tile_w_store(Wt, Wg, K - 1, Jw, lane, wt);
     SG_AST(2)
-    tile_zp(sh, zp, K, lane, zg);   // the diagonal this wave factored last phase
+    tile_zp(sh, zp, K, lane, zg, zw);   // the diagonal this wave factored last phase
     SG_AST(3)
     late = false;
     SG_TSTAMP(13)
@@ -1288,7 +1326,7 @@ __device__ __forceinline__ void tile_phase(f64x4 (&acc)[kTB], double& ypart, int
     SG_TSTAMP(11)
   } else if (act) {
     // (3) back-substitution tile
-    tile_w_store(tile_w(acc[1], Zs, li, lk), Wg, K, J, lane);
+    tile_w_store(tile_w(acc[1], Zs, li, lk), Wg, K, J, lane, wt);
     SG_AST(12)
     SG_TSTAMP(12)
   }
@@ -1300,7 +1338,7 @@ __device__ __forceinline__ void tile_final(f64x4 (&acc)[kTB], int J, bool& late,
                                            double* __restrict__ Wg, const int* tend, int K, int lane, int li,
                                            int lk) {
   if (late) {
-    if (J < tend[K - 1]) tile_w_store(tile_w(acc[0], sh.Zs[(K - 1) & 3], li, lk), Wg, K - 1, J, lane);
+    if (J < tend[K - 1]) tile_w_store(tile_w(acc[0], sh.Zs[(K - 1) & 3], li, lk), Wg, K - 1, J, lane, true);
     late = false;
     return;
   }
@@ -1339,11 +1377,11 @@ __device__ __forceinline__ void sep_write(const f64x4 (&acc)[kTB], double ypart,
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int Rd = C0, Cd = 15 - (lk + 4 * q);   // source (a, b) = (lk + 4q, li) -> (15 - b, 15 - a)
-        dst[(Rd >> 2) * 64 + Cd + 16 * (Rd & 3)] = acc[u][q];
+        st_wt(dst + (Rd >> 2) * 64 + Cd + 16 * (Rd & 3), acc[u][q]);
       }
     }
   }
-  if (lk == 0) sepy[(Io - m) * 16 + 15 - li] = ys;
+  if (lk == 0) st_wt(sepy + (Io - m) * 16 + 15 - li, ys);
 }
 
 // The top half adds the bottom half's separator contribution to the separator columns it holds (before
@@ -1366,7 +1404,7 @@ __device__ __forceinline__ void sep_merge(f64x4 (&acc)[kTB], double& ypart, int 
       use[h] = I >= m;
       const double* src = sepb + (use[h] ? ((I - m) * 7 + (J - m)) * 256 : 0) + lane;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) t[h][q] = src[q * 64];
+      for (int q = 0; q < 4; ++q) t[h][q] = ld_wt(src + q * 64);
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h)
@@ -1374,7 +1412,7 @@ __device__ __forceinline__ void sep_merge(f64x4 (&acc)[kTB], double& ypart, int 
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[u0 + h][q] += t[h][q];
   }
-  if (lk == 0) ypart += sepy[(J - m) * 16 + li];
+  if (lk == 0) ypart += ld_wt(sepy + (J - m) * 16 + li);
 }
 
 // The row sums of one back-substitution step, reduced and scattered: lane (li, lk) holds the partials p[q] of
@@ -1597,7 +1635,7 @@ __device__ __forceinline__ void bs_chain2(const double* __restrict__ Wb, const d
 //     separator rows as usual.
 //   * blockIdx 1 (bottom) runs the phases of B in reversed order (P S P: rows NT-1 .. m+7 of S, then the
 //     separator as its trailing columns, started at zero), writes the separator contribution, its z' and
-//     W tiles, and signals with a release counter.
+//     W tiles write-through (st_wt), and signals with a counter once every wave's stores have landed.
 //   * Back substitution (top workgroup): the separator rows, then A (wave 0) and B (wave 1, reversed W
 //     tiles) side by side.
 // The chain drops from NT tile rows to m + ns (C2: 18 -> 12, C5: 75 -> 42).  The wait is bounded: on a
@@ -1605,6 +1643,9 @@ __device__ __forceinline__ void bs_chain2(const double* __restrict__ Wb, const d
 // instead of hanging or silently rejecting the step.
 //   flags bit 2 (SG_CHOL_FORCE_TIMEOUT, tests only): the bottom workgroup sleeps ~2 ms before its work and
 //   the top one polls at most 256 times, so the time-out path runs deterministically.
+//   flags bits 6, 7 (SG_CHOL_DELAY=bottom|top, tests only): the bottom workgroup sleeps a few tens of µs before
+//   its first phase / the top one just before its poll (the full spin budget: nothing times out), so the hand-off
+//   runs in both arrival orders — the consumer spinning on a late producer, and the flag set before it looks.
 constexpr int kSepSpinMax = 1 << 22;
 template <bool kStamp>
 __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_t* panel_jend,
@@ -1612,6 +1653,9 @@ __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_
                                                              int flags) {
   const LmState* st = d.st;
   unsigned long long tlast = kStamp ? __builtin_amdgcn_s_memtime() : 0ull, tacc[16] = {};
+  const unsigned long long hstart = tlast;
+  unsigned long long hlast = 0ull, hacc[6] = {};
+  bool hchain = false;
   __shared__ TileShared sh;
   extern __shared__ double tdyn[];
   // flags bit 3: the frame part of a system bordered by free intrinsics (order kc0 in S of pitch n): factor it,
@@ -1642,8 +1686,9 @@ __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_
   const bool cand_lds = (flags & 2) != 0;
   CandLds cl;
   cl.carve(tdyn + 32 * NT + (3 * NT + 1) / 2, d.F, d.D, n);
-  // hand-off counter: the bottom half has finished this launch once tflag[0] exceeds the top half's count
-  const int epoch = (nd > 0 && !bottom) ? tflag[1] : 0;
+  // hand-off counters: the bottom half has finished this launch once tflag[0] exceeds the top half's count
+  // (each workgroup reads its own count here, at the launch's start)
+  const int epoch = nd > 0 ? tflag[bottom ? 0 : 1] : 0;
   if (tid == 0) {
     sh.fail = 0;
     sh.tmo = 0;
@@ -1653,6 +1698,8 @@ __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_
   const int spin_max = (flags & 4) ? 256 : kSepSpinMax;
   if (bottom && (flags & 4))
     for (int i = 0; i < 640; ++i) __builtin_amdgcn_s_sleep(127);
+  if (bottom && (flags & 64))
+    for (int i = 0; i < 16; ++i) __builtin_amdgcn_s_sleep(127);
   // Columns J and J+1 (mod 8) on one SIMD: the owner of phase K (column K+1) then shares its SIMD with the
   // late wave of column K (one W tile, a reload) or with column K+2 (its first few tiles), not with a
   // column four ahead and its full band of trailing MFMAs.  SIMD ids from HW_ID; any other placement than
@@ -1734,7 +1781,7 @@ __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_
       } else {
         bad |= tile_diag(D0, y0, sh, zp, 0, lane, li, lk);
       }
-      tile_zp(sh, zp, 0, lane, zg);   // (the wave's own LDS writes: visible to it in order)
+      tile_zp(sh, zp, 0, lane, zg, bottom ? zpg : nullptr);   // (the wave's own LDS writes: visible to it in order)
     }
     else if (cand_lds)   // the seven waves that wait at the first barrier
       cand_prefetch(d, cl, st->cur, (col - 1) * 64 + lane, kTileThreads - 64);
@@ -1754,17 +1801,31 @@ __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_
       const int role = late ? 0 : (J == K + 1 ? 1 : 2);
 #endif
       if (nd > 0 && !bottom && K == m - 1) {
-        // relaxed polls, one acquire (an acquiring poll would invalidate the cache on every round)
-        int spin = 0;
-        while (__hip_atomic_load(tflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= epoch &&
-               ++spin < spin_max)
-          __builtin_amdgcn_s_sleep(1);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        tmo |= spin >= spin_max;
-        sep_merge(acc, ypart, J, m, ns, sepb, sepy, lane, li, lk);
+        // Only the waves that hold a separator column wait (the others have no work left in this workgroup's
+        // phases: their columns lie past the clamped band), each for itself: lane 0 polls (relaxed, agent scope),
+        // and the wave's write-through loads follow its own match, so there is no acquire and no barrier here.  The
+        // bottom's other bytes (W tiles, z', failure slots) are read after the barrier that ends the phases.
+        if (flags & 128)
+          for (int i = 0; i < 16; ++i) __builtin_amdgcn_s_sleep(127);
+        if (kStamp) hlast = __builtin_amdgcn_s_memtime();
+        if (J >= m && J < m + ns) {
+          int spin = 0;
+          if (lane == 0)
+            while (__hip_atomic_load(tflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= epoch &&
+                   ++spin < spin_max)
+              __builtin_amdgcn_s_sleep(1);
+          spin = __builtin_amdgcn_readfirstlane(spin);
+          asm volatile("" ::: "memory");   // (no load of the handed-off bytes moves above the poll)
+          SG_HSTAMP(0)
+          tmo |= spin >= spin_max;
+          sep_merge(acc, ypart, J, m, ns, sepb, sepy, lane, li, lk);
+          if (kStamp) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the stamp after the merge's loads)
+          SG_HSTAMP(1)
+          hchain = J == m;
+        }
       }
       tile_phase<kStamp>(acc, ypart, J, late, bad, tmo, sh, d, Wb, zp, tend, K, NTf, lane, li, lk, ts, zg,
-                         tacc, tlast);
+                         bottom ? zpg : nullptr, tacc, tlast);
       SG_TSTAMP(2)
       // the owner of the next diagonal (now late) is on the critical path until the barrier: it rotates after
       if (!late) tile_rotate(acc);
@@ -1807,24 +1868,41 @@ __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_
 #endif
     if (bottom) {
       // row nd-1's updates of the separator columns (slots of phase nd), then the hand-off
+      if (kStamp) {
+        hlast = __builtin_amdgcn_s_memtime();
+        hacc[5] = hlast - hstart;
+      }
+      // (this wave's failure slot — the 8 slots past z', read by the top half — ahead of the separator stores,
+      // whose registers it would otherwise wait for)
+      if (lane == 0) st_wt(zpg + 16 * nd + wave, bad ? 1.0 : 0.0);
       tile_final(acc, J, late, sh, Wb, tend, nd, lane, li, lk);
       sep_write(acc, ypart, J, nd, NT, m, ns, sepb, sepy, li, lk);
+      SG_HSTAMP(0)
     }
   }
   if (bottom) {
-    if (bad && lane == 0) sh.fail = 1;
-    __syncthreads();   // every owner's z' in LDS
-    for (int i = tid; i < 16 * nd; i += kTileThreads) zpg[i] = zp[i];
-    if (tid == 0) zpg[16 * nd] = sh.fail ? 1.0 : 0.0;   // failure marker (slot past z': read by the top half)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // every wave's hand-off stores, then one signal
+    // Publish: every hand-off byte was stored write-through (the W tiles and z' during the phases, the separator
+    // contribution and each wave's failure slot just now), so there is no L2 write-back: each wave waits for its
+    // own stores to land, and behind the barrier one lane signals with a relaxed store.  (The wait is inline asm:
+    // the compiler may drop a builtin one that it takes for redundant.)
+    SG_HSTAMP(1)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (tid == 0) {
-      const int c = tflag[0];
-      __hip_atomic_store(tflag, c + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    SG_HSTAMP(2)
+    if (tid == 0) __hip_atomic_store(tflag, epoch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    SG_HSTAMP(3)
+    if (kStamp && tid == 0) {
+      unsigned long long* o = d.stamps + kHoStamp + kTraceK * 16;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o[i] += hacc[i];
+      o[4] += 1;
+      o[5] += hacc[5];
     }
     return;
   }
-  if (nd > 0 && zpg[16 * nd] != 0.0) bad = true;
+  // the bottom half's failure slots (write-through loads, behind the barrier of phase m - 1, whose separator
+  // waves had seen the bottom's signal)
+  if (nd > 0 && __any(lane < kTB && ld_wt(zpg + 16 * nd + (lane & (kTB - 1))) != 0.0)) bad = true;
   if (bad && lane == 0) sh.fail = 1;
   __syncthreads();   // W tiles (global) and z' visible to every wave
   SG_TSTAMP(4)
@@ -1844,7 +1922,12 @@ __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_
       }
     } else {
       // separator rows (one wave), then A (waves 0, 1) beside B (waves 2, 3, reversed)
-      if (wave == 0) bs_chain<false>(Wg, zp, xs, m + ns - 1, m, xw, NT, lane, li, lk);
+      // Meanwhile the waves that will read the bottom half's W tiles and z' (plain loads; first touched here,
+      // behind the barrier of phase m - 1) run their agent acquire, off the chain.
+      if (wave == 0)
+        bs_chain<false>(Wg, zp, xs, m + ns - 1, m, xw, NT, lane, li, lk);
+      else if (wave == 2 || wave == 3)
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       __syncthreads();
       if (wave < 2) {
 #pragma unroll
@@ -1891,6 +1974,11 @@ __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_
   SG_TSTAMP(6)
   if (kStamp && lane == 0 && wave < 2)
     for (int s_ = 0; s_ < 16; ++s_) d.stamps[16 * wave + s_] += tacc[s_];
+  if (kStamp && lane == 0 && hchain) {
+    d.stamps[kHoStamp + 0] += hacc[0];
+    d.stamps[kHoStamp + 1] += hacc[1];
+    d.stamps[kHoStamp + 2] += 1;
+  }
 }
 #undef SG_TSTAMP
 

@@ -618,6 +618,14 @@ Envelope PlanEnvelope(const Order& o, const std::vector<int32_t>& lo_blk, const 
 // ================================================================================================
 // Cholesky choice
 
+// The dissected band's hand-off, in phases of the top workgroup's chain: what the bottom workgroup takes beyond its
+// nd phases before the top's separator waves see its signal.  Fitted from the hand-off stamps
+// (profiles/chol_handoff_ab.log): at C2 (m = 7, nd = 6) the top's chain wave waits 1.14 - 1.27 of its phases at the
+// poll of phase m - 1, so nd + h = m + 1.14 .. 1.27 and h = 2.14 .. 2.27, to a quarter phase 2.25 (2.5 before the write-through
+// publish, when the wait was 1.5 phases).  The bottom's own phases are the longer ones (its tiles are loaded
+// transposed), which h carries too.
+constexpr double kHandoffPhases = 2.25;
+
 CholPlan PlanChol(const Order& o, const Envelope& e, const CholGrants& g, const LoadKnobs& k) {
   const int F = o.F, D = o.D, n = o.n, NB = o.NB, nk = o.nk, npanel = e.npanel;
   const std::vector<int32_t>& panel_jmax = e.panel_jmax;
@@ -654,9 +662,9 @@ CholPlan PlanChol(const Order& o, const Envelope& e, const CholGrants& g, const 
   // dissected band: a second workgroup factors the bottom nd tile rows (reversed) while the first factors
   // the top rows [0, m), both meeting at a separator of ns <= 7 tile rows (k_chol_tiles); worth it from about 12
   // tile rows.  The separator must hold every band of the top part: ns(m) = max_{K<m} tend[K] - m.  The chain is
-  // priced in phases as max(m, nd + h) + ns, h = 2.5 phases for the bottom's hand-off (round-2 stamps: nd = 3 / 4 /
-  // 5 at ns = 7 took 198 / 188 / 193 k cycles at C2), and the cheapest m is taken (C2, whose rows are 6-7 tiles
-  // wide: m = 7, ns = 5, nd = 6 — 12 phases on the top chain instead of 14; C5, 8 tiles: ns = 7, nd = 33 as before).
+  // priced in phases as max(m, nd + h) + ns, h = kHandoffPhases for the bottom's hand-off, and the cheapest m is
+  // taken, the smaller separator on a tie (C2, whose rows are 6-7 tiles wide: m = 7, ns = 5, nd = 6 — 12 phases on
+  // the top chain instead of 14; C5, 8 tiles: ns = 7, nd = 33 as before).
   // SG_CHOL_SEP=7: the fixed 7-row separator (tests).
   c.nd = 0;
   c.ns = kTB - 1;
@@ -669,8 +677,8 @@ CholPlan PlanChol(const Order& o, const Envelope& e, const CholGrants& g, const 
       const int ns = fixed7 ? kTB - 1 : reach - m;
       const int nd = npanel - m - ns;
       if (ns < 1 || ns > kTB - 1 || reach - m > ns || nd < 2) continue;
-      const double cost = std::max((double)m, nd + 2.5) + ns;
-      if (cost < best) {
+      const double cost = std::max((double)m, nd + kHandoffPhases) + ns;
+      if (cost < best || (cost == best && ns < c.ns)) {   // ties: the smaller separator
         best = cost;
         c.nd = nd;
         c.ns = ns;

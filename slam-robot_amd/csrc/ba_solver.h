@@ -90,6 +90,12 @@ class BaSolver {
   bool chol_force_tmo_ = getenv("SG_CHOL_FORCE_TIMEOUT") && atoi(getenv("SG_CHOL_FORCE_TIMEOUT")) != 0;
   // SG_CHOL_ZPRE=0: k_chol_tiles factors D_0 itself instead of starting from k_S_reduce's Z_0 (A/B, tests)
   bool chol_zpre_off_ = getenv("SG_CHOL_ZPRE") && atoi(getenv("SG_CHOL_ZPRE")) == 0;
+  // SG_CHOL_DELAY=bottom|top (tests only): that workgroup of the dissected Cholesky sleeps a few tens of µs, the
+  // bottom before its first phase, the top just before its poll, so both arrival orders of the hand-off run
+  int chol_delay_ = !getenv("SG_CHOL_DELAY") ? 0
+                    : std::string(getenv("SG_CHOL_DELAY")) == "bottom" ? 64
+                    : std::string(getenv("SG_CHOL_DELAY")) == "top"    ? 128
+                                                                       : 0;
   bool pack_force_ = getenv("SG_PACK_S") != nullptr;   // pack/unpack S on one rank too (tests the path)
   // speculative linearization (k_update_lin: the candidate pass linearizes at the candidate; k_linearize runs
   // only in a solve's first iteration); SG_SPEC=0: k_point_update + k_linearize every iteration

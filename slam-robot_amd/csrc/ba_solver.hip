@@ -981,7 +981,7 @@ void BaSolver::EnqueueIterations(int n) {
     TimedLaunchBegin(kKChol);
     if (chol_.tiles)
       LaunchCholTiles(d.stamps != nullptr, dim3(chol_.nd > 0 ? 2 : 1), d,
-                      (chol_.cand_lds ? 2 : 0) | (chol_force_tmo_ ? 4 : 0) | (zpre ? 16 : 0));
+                      (chol_.cand_lds ? 2 : 0) | (chol_force_tmo_ ? 4 : 0) | (zpre ? 16 : 0) | chol_delay_);
     else if (chol_.window)
       LaunchCholWindowK(d.stamps != nullptr, stream_, d, (const int32_t*)work_i_.ptr, rdg_.ptr);
     else
