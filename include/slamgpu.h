@@ -251,6 +251,9 @@ typedef struct sg_ba_info {
   int32_t lin_waves;                         /* waves per Jacobian-sweep chunk (1, or 2 when the doubled grid
                                                 fits the device at once) */
   int32_t cholesky_separator;                /* tiled path with a split: the separator's tile rows (<= 7) */
+  int32_t cholesky_stile;                    /* tiled path: the last LM iteration enqueued loaded its tiles from the
+                                                tile-major copy of the band that the S reduce writes (1), or from
+                                                row-major S (0: landmark shards, packed S, SG_CHOL_STILE=0) */
 } sg_ba_info;
 int sg_ba_info_get(const sg_ba* h, sg_ba_info* out);
 

@@ -1010,11 +1010,28 @@ struct TileSrc {
   int sep;   // first separator tile row (reversed side only; the top half passes NT)
   int nb;    // rows / columns factored
   int ld;    // pitch of S
+  // kStile (flags bit 5): the tiles come from St, k_S_reduce's tile-major copy of the band (ba_plan.h: PlanStile),
+  // this workgroup's tiles in its own order and in the accumulator layout, padding and zeros baked in
+  const double* St;
+  int sbase;   // the workgroup's first slot (0, or NT kTB for the reversed side)
+  int srow;    // tile rows it reads from St (the reversed side: nd, its separator tiles start at zero)
+  int scol;    // ... and columns (the rows it factors; the reversed side: and its separator columns, nd + ns)
+  int szero;   // the slot that is never written
 };
 
+// kStile: tile (I, J) is slot sbase + I kTB + (J - I) of St, lane l's register q at 64 q + l: four loads of one
+// 512-byte line each, no per-element select; a tile outside the workgroup's rows or columns is the zero slot.
+template <bool kStile>
 __device__ __forceinline__ f64x4 tile_load(const double* __restrict__ S, int I, int J, int li, int lk,
                                            const TileSrc& ts) {
   f64x4 t;
+  if (kStile) {
+    const bool in = I >= 0 && I < ts.srow && J < ts.scol;
+    const double* src = ts.St + (size_t)(in ? ts.sbase + I * kTB + (J - I) : ts.szero) * 256 + 16 * lk + li;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) t[q] = src[64 * q];
+    return t;
+  }
   const int n = ts.nb, ld = ts.ld;
   const int cz = ld * ld + ld;
   const bool zsep = I >= ts.sep && J >= ts.sep;
@@ -1173,10 +1190,11 @@ __device__ __forceinline__ void tile_rotate(f64x4 (&acc)[kTB]) {
 }
 
 // Column J of S into the slots of phase K (slot s: row J - ((J - (s + K - 1)) & 7)).
+template <bool kStile>
 __device__ __forceinline__ void tile_col_load(f64x4 (&acc)[kTB], double& ypart, const Dev& d, int J, int K,
                                               int li, int lk, const TileSrc& ts) {
 #pragma unroll
-  for (int u = 0; u < kTB; ++u) acc[u] = tile_load(d.S, J - ((J - (u + K - 1)) & 7), J, li, lk, ts);
+  for (int u = 0; u < kTB; ++u) acc[u] = tile_load<kStile>(d.S, J - ((J - (u + K - 1)) & 7), J, li, lk, ts);
   const int gj = 16 * J + li, ld = ts.ld;
   const int sj = ts.rev ? ts.np - 1 - gj : gj;
   ypart = d.S[(lk == 0 && sj < ts.nb && J < ts.sep) ? ld * ld + sj : ld * ld + ld];
@@ -1193,7 +1211,7 @@ __device__ __forceinline__ bool la_done(const int* tend, int Kp) {   // look-ahe
   return Kp >= 0 && Kp + 2 < tend[Kp];
 }
 
-template <bool kStamp>
+template <bool kStamp, bool kStile>
 __device__ __forceinline__ void tile_phase(f64x4 (&acc)[kTB], double& ypart, int& J, bool& late, bool& bad,
                                            bool& tmo, TileShared& sh, const Dev& d,
                                            double* __restrict__ Wg, double* zp, const int* tend, int K, int NT,
@@ -1215,7 +1233,7 @@ __device__ __forceinline__ void tile_phase(f64x4 (&acc)[kTB], double& ypart, int
     const int Jw = J;
     J += kTB;
 #ifndef SG_X_NOLOAD   // timing-only A/B (round 6): no column reload (results wrong)
-    tile_col_load(acc, ypart, d, J, K, li, lk, ts);
+    tile_col_load<kStile>(acc, ypart, d, J, K, li, lk, ts);
 #endif
     SG_AST(1)
     if (hasw) tile_w_store(Wt, Wg, K - 1, Jw, lane, wt);
@@ -1643,11 +1661,15 @@ __device__ __forceinline__ void bs_chain2(const double* __restrict__ Wb, const d
 // instead of hanging or silently rejecting the step.
 //   flags bit 2 (SG_CHOL_FORCE_TIMEOUT, tests only): the bottom workgroup sleeps ~2 ms before its work and
 //   the top one polls at most 256 times, so the time-out path runs deterministically.
+//   flags bit 5 (the kStile instances, chosen by the launcher): both workgroups load their tiles from St, where
+//   k_S_reduce has put them in factor order and accumulator layout (the bottom's already reversed and transposed), and
+//   the bottom reads its band ends as planned; the rhs still comes from S's rhs row.  Set where k_S_reduce is S's last
+//   writer (as flags bit 4); SG_CHOL_STILE=0 keeps the loader of row-major S.
 //   flags bits 6, 7 (SG_CHOL_DELAY=bottom|top, tests only): the bottom workgroup sleeps a few tens of µs before
 //   its first phase / the top one just before its poll (the full spin budget: nothing times out), so the hand-off
 //   runs in both arrival orders — the consumer spinning on a late producer, and the flag set before it looks.
 constexpr int kSepSpinMax = 1 << 22;
-template <bool kStamp>
+template <bool kStamp, bool kStile>
 __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_t* panel_jend,
                                                              double* __restrict__ Wg, int32_t* tflag, int nd,
                                                              int flags) {
@@ -1674,7 +1696,8 @@ __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_
   double* zpg = Wg + (size_t)2 * NT * kTB * 256;   // [16 nd] the bottom half's z'
   double* sepb = zpg + 16 * NT;                     // [49][256] separator contribution
   double* sepy = sepb + 49 * 256;                   // [7][16]   its rhs
-  const TileSrc ts{bottom ? 1 : 0, 16 * NT, bottom ? nd : (1 << 28), n, d.n};
+  const TileSrc ts{bottom ? 1 : 0, 16 * NT, bottom ? nd : (1 << 28), n, d.n,
+                   d.St, bottom ? NT * kTB : 0, bottom ? nd : NTf, bottom ? nd + ns : NTf, 2 * NT * kTB};
   double* zg = border ? Wb : nullptr;
   double* xs = tdyn;              // [16 NT] back-substitution solution
   double* zp = tdyn + 16 * NT;    // [16 NT] Z_K^T z_K
@@ -1716,7 +1739,7 @@ __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_
     for (int q = 0; q < 4; ++q) D0[q] = d.zpre[(lk + 4 * q) * 16 + li];
     zbad = d.zpre[256] != 0.0;
   } else {
-    D0 = tile_load(d.S, 0, 0, li, lk, ts);
+    D0 = tile_load<kStile>(d.S, 0, 0, li, lk, ts);
   }
   double y0;
   {
@@ -1750,11 +1773,14 @@ __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_
     bool late = false;
     // column 0's wave loads column 8 instead (D_0 is in flight) and factors D_0 while it arrives
     if (J == 0) J = kTB;
-    tile_col_load(acc, ypart, d, J, 0, li, lk, ts);   // slots of phase 0
+    tile_col_load<kStile>(acc, ypart, d, J, 0, li, lk, ts);   // slots of phase 0
     // band ends (read first in phase 0, after the barrier below): their loads follow the column's
     for (int k = tid; k < NT; k += kTileThreads) {
       if (!bottom) {
         tend[k] = min((panel_jend[k] + 15) >> 4, NTf);
+      } else if (kStile) {
+        // the reversed rows' band ends, planned on the host (PlanStile) behind the tiles' slots
+        tend[k] = min(d.stile_dst[2 * max(d.nstile, 1) + k], nd + ns);
       } else {
         // reversed row k = column c = NT-1-k of S: its band reaches back to lo(c), the first row whose band
         // covers c (band ends are non-decreasing), so the reversed row ends at NT - lo(c)
@@ -1824,7 +1850,7 @@ __global__ __launch_bounds__(kTileThreads) void k_chol_tiles(Dev d, const int32_
           hchain = J == m;
         }
       }
-      tile_phase<kStamp>(acc, ypart, J, late, bad, tmo, sh, d, Wb, zp, tend, K, NTf, lane, li, lk, ts, zg,
+      tile_phase<kStamp, kStile>(acc, ypart, J, late, bad, tmo, sh, d, Wb, zp, tend, K, NTf, lane, li, lk, ts, zg,
                          bottom ? zpg : nullptr, tacc, tlast);
       SG_TSTAMP(2)
       // the owner of the next diagonal (now late) is on the critical path until the barrier: it rotates after
@@ -2321,7 +2347,10 @@ __global__ __launch_bounds__(kBordThreads) void k_chol_border(Dev d, double* __r
 // ------------------------------------------------------------------------------------------------
 // host launchers (ba_launch.h)
 
-static const void* const kCholTilesKernels[] = {(const void*)k_chol_tiles<false>, (const void*)k_chol_tiles<true>};
+// [2 stile + stamp]
+static const void* const kCholTilesKernels[] = {
+    (const void*)k_chol_tiles<false, false>, (const void*)k_chol_tiles<true, false>,
+    (const void*)k_chol_tiles<false, true>, (const void*)k_chol_tiles<true, true>};
 
 void CholSetAttributes(size_t* tile_lds, size_t* gchol_lds, size_t* border_lds) {
   SG_HIP_CHECK(hipFuncSetAttribute((const void*)k_cholesky_window<false>,
@@ -2361,7 +2390,8 @@ void LaunchCholTilesK(bool stamp, dim3 grid, size_t lds, hipStream_t s, const De
                       double* Wg, int32_t* tflag, int nd, int flags) {
   Dev dd = d;
   void* args[] = {&dd, &panel_jend, &Wg, &tflag, &nd, &flags};
-  SG_HIP_CHECK(hipLaunchKernel(kCholTilesKernels[stamp ? 1 : 0], grid, dim3(kTileThreads), args, lds, s));
+  const void* f = kCholTilesKernels[((flags & 32) ? 2 : 0) + (stamp ? 1 : 0)];
+  SG_HIP_CHECK(hipLaunchKernel(f, grid, dim3(kTileThreads), args, lds, s));
 }
 
 void LaunchCholBorderK(int border_flags, size_t lds, hipStream_t s, const Dev& d, double* Wg) {

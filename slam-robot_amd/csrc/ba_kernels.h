@@ -130,6 +130,9 @@ struct Dev {
   const int32_t* s_lidx;
   const int32_t* stile;          // [nstile] band tiles (R << 16) | C, R <= C, of the frame columns
   int32_t nstile;
+  const int32_t* stile_dst;      // [nstile][2] slot of the tile in St for the top / the bottom workgroup of k_chol_tiles,
+                                 // or -1 (PlanStile), then [NT] the bottom's reversed band ends
+  double* St;                    // tile-major copy of the band in k_chol_tiles' accumulator layout (ba_plan.h: PlanStile)
   const int32_t* r_loff;         // [NB]: per block, the count of its rhs partials in S_slab (offsets: r_lidx rows of
                                  // r_lstride, a multiple of 256)
   const int32_t* r_lidx;

@@ -133,6 +133,11 @@ SG_LAYOUT_HD constexpr size_t border_lds_doubles(int NT, int flags, int F, int D
   if (flags & 2) o += (cand_lds_bytes(F, D, n) + 7) / 8;
   return o;
 }
+// St, the tile-major copy of S's band (ba_plan.h: PlanStile): slots of 256 doubles, two per tile of the NT kTB
+// band positions (top and bottom workgroup) and one that stays zero; element (a, b) of a slot sits where lane
+// 16 (a & 3) + b holds it in register a >> 2 of a k_chol_tiles accumulator.
+SG_LAYOUT_HD constexpr size_t stile_doubles(int NT) { return ((size_t)2 * NT * kTB + 1) * 256; }
+SG_LAYOUT_HD constexpr int stile_elem(int a, int b) { return 64 * (a >> 2) + 16 * (a & 3) + b; }
 
 }  // namespace sg
 

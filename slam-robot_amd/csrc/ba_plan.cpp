@@ -622,8 +622,13 @@ Envelope PlanEnvelope(const Order& o, const std::vector<int32_t>& lo_blk, const 
 // nd phases before the top's separator waves see its signal.  Fitted from the hand-off stamps
 // (profiles/chol_handoff_ab.log): at C2 (m = 7, nd = 6) the top's chain wave waits 1.14 - 1.27 of its phases at the
 // poll of phase m - 1, so nd + h = m + 1.14 .. 1.27 and h = 2.14 .. 2.27, to a quarter phase 2.25 (2.5 before the write-through
-// publish, when the wait was 1.5 phases).  The bottom's own phases are the longer ones (its tiles are loaded
-// transposed), which h carries too.
+// publish, when the wait was 1.5 phases).  The bottom's own phases were the longer ones (its tiles were loaded
+// transposed), which h carried too.
+// With the tiles read from St (PlanStile; profiles/chol_stile_ab.log) the wait at C2 is 6.2 - 6.7 k cycles of a 9.3 k
+// phase, h = 1.67 - 1.72, to a quarter phase 1.75.  The price stays at 2.25 all the same.  Half a phase less on the
+// bottom's side lowers no candidate by more than 0.5, so C2's split (13.25 now, 12.75 then) stays the cheapest, and
+// C5 takes m = 35 at either price; but the fixed 7-row separator of the tests (SG_CHOL_SEP=7) is pinned to
+// nd = (NT - 9) / 2, which at C2's 18 tile rows needs h > 2.
 constexpr double kHandoffPhases = 2.25;
 
 CholPlan PlanChol(const Order& o, const Envelope& e, const CholGrants& g, const LoadKnobs& k) {
@@ -687,8 +692,8 @@ CholPlan PlanChol(const Order& o, const Envelope& e, const CholGrants& g, const 
   }
   if (c.tiles) {
     // W tiles of the top and bottom halves, the bottom's z' (+ failure slot), the separator contribution
-    // and its rhs, then the constants {0, 1}
-    c.wg_size = (size_t)2 * npanel * kTB * 256 + 16 * (size_t)npanel + 49 * 256 + 7 * 16 + 2;
+    // and its rhs, the tile-major band St (PlanStile), then the constants {0, 1}
+    c.wg_size = (size_t)2 * npanel * kTB * 256 + 16 * (size_t)npanel + 49 * 256 + 7 * 16 + stile_doubles(npanel) + 2;
     c.tile_lds = (size_t)npanel * 32 * sizeof(double) + (size_t)(3 * npanel + 1) / 2 * sizeof(double);
     c.cand_lds = !c.border && F <= kCandMax && D <= kCandMax &&
                  c.tile_lds + cand_lds_bytes(F, D, n) <= 100 * 1024 &&
@@ -701,6 +706,37 @@ CholPlan PlanChol(const Order& o, const Envelope& e, const CholGrants& g, const 
     }
   }
   return c;
+}
+
+// Where k_S_reduce's band tiles go in St (ba_plan.h), and the band ends of the reversed matrix the bottom
+// workgroup factors.  Meaningful for the tiled Cholesky without border (nk = 0: the frame tiles are all of S).
+StilePlan PlanStile(const Envelope& e, const CholPlan& c) {
+  StilePlan s;
+  const int NT = e.npanel;
+  s.dst.assign(2 * (size_t)std::max(e.nstile, 1), -1);
+  s.tend_rev.assign(std::max(NT, 1), 0);
+  if (!c.tiles || c.border) return s;
+  const int top_end = c.nd > 0 ? NT - c.nd : NT;   // m + ns: rows and columns of the top workgroup
+  for (int t = 0; t < e.nstile; ++t) {
+    const int R = e.stile[t] >> 16, C = e.stile[t] & 0xffff;
+    if (C - R >= kTB || C >= NT) continue;
+    if (C < top_end) {
+      s.dst[2 * t] = R * kTB + (C - R);
+    } else if (NT - 1 - R < c.nd + c.ns) {   // (a band tile of a column >= m + ns starts at a separator row or below)
+      const int Ir = NT - 1 - C;
+      s.dst[2 * t + 1] = NT * kTB + Ir * kTB + (C - R);
+    }
+  }
+  std::vector<int> tend(NT);
+  for (int R = 0; R < NT; ++R) tend[R] = std::min(NT, (e.panel_jmax[R] + kCholNb - 1) / kCholNb);
+  for (int k = 0; k < NT; ++k) {
+    const int col = NT - 1 - k;
+    int lo = col;
+    for (int R = col - 1; R >= 0; --R)
+      if (tend[R] > col) lo = R;
+    s.tend_rev[k] = NT - lo;
+  }
+  return s;
 }
 
 }  // namespace sg

@@ -127,6 +127,24 @@ struct CholPlan {
 };
 CholPlan PlanChol(const Order& o, const Envelope& e, const CholGrants& g, const LoadKnobs& k);
 
+// St, the tile-major copy of S's band that k_S_reduce writes beside S and k_chol_tiles loads its tiles from: slots of
+// 256 doubles in the accumulator layout (lane l = 16 lk + li, register q at 256 slot + 64 q + l: element (lk + 4q,
+// li)), each workgroup's tiles in its own factor order.
+//   top half, slots [0, NT kTB): slot I kTB + (J - I) is tile (I, J) of S, for the rows and columns the top
+//     workgroup factors (all of S without a split, < m + ns with one);
+//   bottom half, slots [NT kTB, 2 NT kTB): slot NT kTB + I' kTB + (J' - I') is tile (I', J') of P S P (index i ->
+//     16 NT - 1 - i), rows I' < nd: S tile (R, C) = (NT-1-J', NT-1-I'), C >= m + ns, element (a, b) -> (15-b, 15-a);
+//   slot 2 NT kTB: never written (zero), what a load of a tile outside a workgroup's rows or columns reads.
+// Band tiles get one slot each (the separator block belongs to the top only: the bottom starts it at zero); the
+// other slots stay zero from the load.  Padding past n is written as the identity.  (stile_doubles, stile_elem:
+// ba_layout.h)
+struct StilePlan {
+  std::vector<int32_t> dst;        // [max(nstile, 1)][2] per Envelope::stile entry: top slot or -1, bottom slot or -1
+  std::vector<int32_t> tend_rev;   // [NT] band end (tiles, exclusive, unclamped) of row k of P S P: NT - lo(NT-1-k),
+                                   // lo(c) the first tile row of S whose band covers column c
+};
+StilePlan PlanStile(const Envelope& e, const CholPlan& c);
+
 }  // namespace sg
 
 #endif  // SG_BA_PLAN_H_

@@ -681,9 +681,21 @@ __device__ __forceinline__ double s_tile_elem(const Dev& d, const double (&wsum)
   return t;
 }
 
-// pre: the workgroup of tile (0, 0) also factors it (tile_factor, as k_chol_tiles' first owner would) into
+// One element of a band tile into its slot of St (ba_plan.h: PlanStile), thread (ti, tj) = (tid >> 4, tid & 15) of the
+// tile's workgroup: the top workgroup's slot in the accumulator layout (element (ti, tj) at 64 (ti >> 2) + 16 (ti & 3)
+// + tj, which is tid: one 512-byte line per wave), the bottom's reversed and transposed, (15 - tj, 15 - ti).
+__device__ __forceinline__ void s_tile_st(const Dev& d, int2 sd, int tid, double v) {
+  const int ti = tid >> 4, tj = tid & 15;
+  if (sd.x >= 0) d.St[(size_t)256 * sd.x + stile_elem(ti, tj)] = v;
+  if (sd.y >= 0) d.St[(size_t)256 * sd.y + stile_elem(15 - tj, 15 - ti)] = v;
+}
+
+// pre bit 0: the workgroup of tile (0, 0) also factors it (tile_factor, as k_chol_tiles' first owner would) into
 // d.zpre: Z_0 = U_00^-T row-major [16][16], then a failure marker; k_chol_tiles (flags bit 4) starts from it, so
 // the 16-pivot factor of D_0 is off the Cholesky's opening path (one rank, no free intrinsics: S is final here).
+// pre bit 1: every band tile also goes to its slot of St (d.stile_dst, read beside d.stile), what k_chol_tiles (flags
+// bit 5) loads instead of S: the value stored to S (0 below the diagonal of a diagonal tile), and past the system's
+// order the identity, which k_chol_tiles' loader pads S with.
 __global__ __launch_bounds__(256) void k_S_reduce(Dev d, int amode, int pre) {
   // LmState is read beside the first work-list loads, not ahead of them: the done test comes after the
   // partial walk (a finished solve's trailing launches walk once more; every other launch saves a round trip)
@@ -696,6 +708,7 @@ __global__ __launch_bounds__(256) void k_S_reduce(Dev d, int amode, int pre) {
   const int nf = 6 * d.NB;   // frame columns
   if (wv < d.nstile) {
     const int rc = d.stile[wv];
+    const int2 sd = (pre & 2) ? reinterpret_cast<const int2*>(d.stile_dst)[wv] : make_int2(-1, -1);
     const int R = rc >> 16, C = rc & 0xffff;
     const int i = 16 * R + (tid >> 4), j = 16 * C + (tid & 15);
     const bool live = i < nf && j < nf;
@@ -749,7 +762,7 @@ __global__ __launch_bounds__(256) void k_S_reduce(Dev d, int amode, int pre) {
 #pragma unroll
     for (int m = 0; m < 4; ++m) wsum[part][lane + 64 * m] = s[m];
     __syncthreads();
-    if (pre && rc == 0) {   // tile (0, 0), factored here (a workgroup-uniform branch: its barrier is safe)
+    if ((pre & 1) && rc == 0) {   // tile (0, 0), factored here (a workgroup-uniform branch: its barrier is safe)
       __shared__ double Dt[16 * kTLd], It[16 * kTLd], Yt[16], prt[2 * kCholNb];
       double t = 0.0;
       if (!done && live && up) t = s_tile_elem(d, wsum, tid, gi, e_acc, amode, I, Jb, a, c, e_u, e_fd, e_si, e_sj,
@@ -758,6 +771,7 @@ __global__ __launch_bounds__(256) void k_S_reduce(Dev d, int amode, int pre) {
         d.S[gi] = 0.0;
         if (d.nwide) d.S_wide[gi] = 0.0;
       }
+      if (!done) s_tile_st(d, sd, tid, live ? t : (i == j ? 1.0 : 0.0));
       // as k_chol_tiles' tile_load pads past the system: 1 on the diagonal, 0 elsewhere
       const int ti = tid >> 4, tj = tid & 15;
       Dt[ti * kTLd + tj] = live ? (up ? t : 0.0) : (ti == tj ? 1.0 : 0.0);
@@ -774,13 +788,19 @@ __global__ __launch_bounds__(256) void k_S_reduce(Dev d, int amode, int pre) {
       }
       return;
     }
-    if (done || !live) return;
+    if (done) return;
+    if (!live) {
+      s_tile_st(d, sd, tid, i == j ? 1.0 : 0.0);
+      return;
+    }
     if (!up) {
       d.S[gi] = 0.0;
       if (d.nwide) d.S_wide[gi] = 0.0;   // schur_pair_add also adds a diagonal block's lower half: keep it clean
+      s_tile_st(d, sd, tid, 0.0);
       return;
     }
-    s_tile_elem(d, wsum, tid, gi, e_acc, amode, I, Jb, a, c, e_u, e_fd, e_si, e_sj, e_dg, e_x, radius);
+    s_tile_st(d, sd, tid,
+              s_tile_elem(d, wsum, tid, gi, e_acc, amode, I, Jb, a, c, e_u, e_fd, e_si, e_sj, e_dg, e_x, radius));
     return;
   }
   // rhs block I: one wave per 64-entry chunk of its partial list (in list order), lanes 0..5

@@ -90,6 +90,9 @@ class BaSolver {
   bool chol_force_tmo_ = getenv("SG_CHOL_FORCE_TIMEOUT") && atoi(getenv("SG_CHOL_FORCE_TIMEOUT")) != 0;
   // SG_CHOL_ZPRE=0: k_chol_tiles factors D_0 itself instead of starting from k_S_reduce's Z_0 (A/B, tests)
   bool chol_zpre_off_ = getenv("SG_CHOL_ZPRE") && atoi(getenv("SG_CHOL_ZPRE")) == 0;
+  // SG_CHOL_STILE=0: k_chol_tiles loads its tiles from row-major S instead of k_S_reduce's tile-major copy (A/B, tests)
+  bool chol_stile_off_ = getenv("SG_CHOL_STILE") && atoi(getenv("SG_CHOL_STILE")) == 0;
+  bool chol_stile_last_ = false;   // the last LM iteration enqueued took that copy (sg_ba_info.cholesky_stile)
   // SG_CHOL_DELAY=bottom|top (tests only): that workgroup of the dissected Cholesky sleeps a few tens of µs, the
   // bottom before its first phase, the top just before its poll, so both arrival orders of the hand-off run
   int chol_delay_ = !getenv("SG_CHOL_DELAY") ? 0
@@ -178,7 +181,7 @@ class BaSolver {
   DBuf<double> seg_fail_;
   DBuf<SchurBatch> sbatch_;
   DBuf<WideSeg> wsegs_;
-  DBuf<int32_t> pinfo_, pmx_, cells_, cell_obs_, stile_;
+  DBuf<int32_t> pinfo_, pmx_, cells_, cell_obs_, stile_, stile_dst_;
   DBuf<double> rdg_;       // 1/U_jj of the factor
   DBuf<double> mk_, mq_, mt_, mX_, mobs_pt_, mobs_err_, mred_;
   HostIo io_;   // ReprojectMap's uploads and downloads (hostio.h)

@@ -357,6 +357,11 @@ void BaSolver::Load(const sg_problem& p) {
   stg.Add(cells_, wl.cells);
   stg.Add(cell_obs_, wl.cell_obs);
   stg.Add(stile_, env.stile);
+  {   // the tiles' slots in St, then the bottom workgroup's band ends (one list: Dev::stile_dst)
+    StilePlan sp = PlanStile(env, chol_);
+    sp.dst.insert(sp.dst.end(), sp.tend_rev.begin(), sp.tend_rev.end());
+    stg.Add(stile_dst_, sp.dst);
+  }
   stg.Add(pairs_, wl.pairs);
   seg_fail_.Resize(std::max(wl.nseg + wl.nwide, 1));
   stg.Add(cam_loff_, wl.cam_loff);
@@ -433,6 +438,7 @@ void BaSolver::Load(const sg_problem& p) {
   if (host_timing) lap_log += LoadDeviceTimes(load_t0, idle_valid_prev, idle_gap_host);
   SaveStructure(p);
   full_loads_++;
+  chol_stile_last_ = false;
   if (host_timing) {
     SG_HIP_CHECK(hipStreamSynchronize(stream_));
     lap("sync");
@@ -720,6 +726,10 @@ Dev BaSolver::MakeDev() {
   d.nwide = wk_.nwide;
   d.stile = stile_.ptr;
   d.nstile = env_.nstile;
+  d.stile_dst = stile_dst_.ptr;
+  // St follows the separator terms in Wg_ (PlanChol: wg_size)
+  const size_t npan = (size_t)(n_ + kCholNb - 1) / kCholNb;
+  d.St = chol_.wg_size ? Wg_.ptr + 2 * npan * kTB * 256 + 16 * npan + 49 * 256 + 7 * 16 : nullptr;
   d.seg_fail = seg_fail_.ptr;
   d.pairs = reinterpret_cast<const int2*>(pairs_.ptr);
   d.assemble = (!comm_ || comm_->rank() == 0) ? 1 : 0;
@@ -951,7 +961,11 @@ void BaSolver::EnqueueIterations(int n) {
     // rank is a copy): it also factors the first diagonal tile for k_chol_tiles (flags bit 4)
     const int samode = merged ? 2 : (d.assemble ? 1 : 0);
     const bool zpre = chol_.tiles && !chol_.border && nk_ == 0 && samode == 1 && !(multi_x || merged) && !chol_zpre_off_;
-    LaunchSReduceK(std::max(nwv, 1), stream_, d, samode, zpre ? 1 : 0);
+    // ... and writes the band a second time, tile-major in the order and layout k_chol_tiles consumes (St; flags bit 5)
+    const bool stile = chol_.tiles && !chol_.border && nk_ == 0 && samode == 1 && !(multi_x || merged) && !pack_force_ &&
+                       !chol_stile_off_;
+    chol_stile_last_ = stile;
+    LaunchSReduceK(std::max(nwv, 1), stream_, d, samode, (zpre ? 1 : 0) | (stile ? 2 : 0));
     TimedLaunchEnd(kKSReduce);
     if (nk_) {
       LaunchIntrSchurK(stream_, d, n_, nk_, NB_, ncam_, P_, wk_.intr_nsl);
@@ -981,7 +995,7 @@ void BaSolver::EnqueueIterations(int n) {
     TimedLaunchBegin(kKChol);
     if (chol_.tiles)
       LaunchCholTiles(d.stamps != nullptr, dim3(chol_.nd > 0 ? 2 : 1), d,
-                      (chol_.cand_lds ? 2 : 0) | (chol_force_tmo_ ? 4 : 0) | (zpre ? 16 : 0) | chol_delay_);
+                      (chol_.cand_lds ? 2 : 0) | (chol_force_tmo_ ? 4 : 0) | (zpre ? 16 : 0) | (stile ? 32 : 0) | chol_delay_);
     else if (chol_.window)
       LaunchCholWindowK(d.stamps != nullptr, stream_, d, (const int32_t*)work_i_.ptr, rdg_.ptr);
     else
@@ -1245,6 +1259,7 @@ void BaSolver::Info(sg_ba_info* o) const {
   o->num_allreduces = nallreduce_;
   o->lin_waves = wk_.lin_waves;
   o->cholesky_separator = chol_.tiles && chol_.nd > 0 ? chol_.ns : 0;
+  o->cholesky_stile = chol_stile_last_ ? 1 : 0;
 }
 
 double BaSolver::ReprojectMap(sg_map* m) {
