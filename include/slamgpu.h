@@ -254,6 +254,8 @@ typedef struct sg_ba_info {
   int32_t cholesky_stile;                    /* tiled path: the last LM iteration enqueued loaded its tiles from the
                                                 tile-major copy of the band that the S reduce writes (1), or from
                                                 row-major S (0: landmark shards, packed S, SG_CHOL_STILE=0) */
+  int32_t wt_stores;                         /* launch outputs stored write-through: bit 0 the Jacobian records,
+                                                bit 1 the camera partials, bit 2 the Schur slabs (SG_WT_STORES) */
 } sg_ba_info;
 int sg_ba_info_get(const sg_ba* h, sg_ba_info* out);
 

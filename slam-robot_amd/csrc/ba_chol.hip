@@ -3,6 +3,7 @@
 // poses), the bordered band of free intrinsics k_chol_border, and the window / global Cholesky for other shapes.
 #include "ba_lm.h"
 #include "ba_tile.h"
+#include "wt_store.h"
 
 namespace sg {
 
@@ -1081,13 +1082,7 @@ __device__ __forceinline__ bool tile_diag(const f64x4& D, double ypart, TileShar
 // contribution and the failure slots are read by the matching loads (sc1: served past the reading CU's L1), every
 // load of them, each wave after its own poll has matched or behind a barrier that follows it: no L1 invalidate on
 // the chain.  The W tiles and z' are read only in the back substitution, by plain loads behind an agent acquire
-// that their waves run off the chain.
-__device__ __forceinline__ void st_wt(double* p, double v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double ld_wt(const double* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// that their waves run off the chain.  (st_wt, ld_wt: wt_store.h)
 
 // z'_K = Z_K^T z_K for the back substitution, from the posted Z_K and z_K (LDS ring slot K & 3): formed by
 // the owner one phase later (its late phase), off the pivot chain.

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "project_math.h"
 #include "schur_tiles.h"
+#include "wt_store.h"
 
 namespace sg {
 
@@ -167,7 +168,31 @@ __device__ __forceinline__ double2 jload2(const double* J, int o, int e2) {
   return reinterpret_cast<const double2*>(J)[jidx2(o, e2)];
 }
 // Write one observation's record (rr, Jc rotation columns, Jp) — the translation columns are implied.
+// kWt (Dev::wt & kWtJ): the eight pairs as write-through stores (wt_store.h).  The sweeps store the slot they
+// linearize into and read only the other one (k_linearize reads no record at all, k_update_lin reads J[cur] and
+// stores J[cur ^ 1]), so no instruction of the storing launch reads these bytes.  A template parameter of the
+// sweeps, not a branch: a wave-uniform branch here ends the block in which the stores are scheduled among the LDS
+// atomics that follow, 0.3 us of k_update_lin at C2 (profiles/sweep_wt_stagger_ab.log D, H).
+__device__ __forceinline__ void jstore_wt(double* J, int o, const double (&v)[2 * kJPairs]) {
+  static_assert(kJPairs == 8, "pair e2 at byte 1024 e2 - 4096 of the record's middle");
+  const double2* Jm = reinterpret_cast<const double2*>(J) + jidx2(o, 0) + 64 * 4;   // one address, eight offsets
+  st_wt16<-4096>(Jm, v[0], v[1]);
+  st_wt16<-3072>(Jm, v[2], v[3]);
+  st_wt16<-2048>(Jm, v[4], v[5]);
+  st_wt16<-1024>(Jm, v[6], v[7]);
+  st_wt16<0>(Jm, v[8], v[9]);
+  st_wt16<1024>(Jm, v[10], v[11]);
+  st_wt16<2048>(Jm, v[12], v[13]);
+  st_wt16<3072>(Jm, v[14], v[15]);
+}
+template <bool kWt>
 __device__ __forceinline__ void jstore(double* J, int o, const double* rr, const double* Jc, const double* Jp) {
+  if (kWt) {
+    const double v[2 * kJPairs] = {rr[0], rr[1], Jc[0], Jc[1], Jc[2], Jc[6], Jc[7], Jc[8],
+                                   Jp[0], Jp[1], Jp[2], Jp[3], Jp[4], Jp[5], Jp[6], Jp[7]};
+    jstore_wt(J, o, v);
+    return;
+  }
   double2* Jo = reinterpret_cast<double2*>(J) + jidx2(o, 0);   // pair e2 at Jo[64 e2]
   Jo[0] = make_double2(rr[0], rr[1]);
   Jo[64 * 1] = make_double2(Jc[0], Jc[1]);
@@ -176,7 +201,13 @@ __device__ __forceinline__ void jstore(double* J, int o, const double* rr, const
 #pragma unroll
   for (int i = 0; i < 4; ++i) Jo[64 * (4 + i)] = make_double2(Jp[2 * i], Jp[2 * i + 1]);
 }
+template <bool kWt>
 __device__ __forceinline__ void jstore_zero(double* J, int o) {
+  if (kWt) {
+    const double v[2 * kJPairs] = {};
+    jstore_wt(J, o, v);
+    return;
+  }
   double2* Jo = reinterpret_cast<double2*>(J) + jidx2(o, 0);
 #pragma unroll
   for (int i = 0; i < kJPairs; ++i) Jo[64 * i] = make_double2(0.0, 0.0);

@@ -194,6 +194,7 @@ struct Dev {
   const int32_t* intr_boff;      // [NB + 2] per frame block (then the fixed frames' block NB): observations
   const int32_t* intr_bidx;      //   of non-fixed observations, in observation order
   double stab_b, stab_inv_b;     // CauchyLoss(stab_range): b = stab_range^2
+  int32_t wt;                    // kWt* bits (ba_layout.h): launch outputs stored write-through (SG_WT_STORES)
 };
 constexpr int kMaxIntrCams = 4;  // cameras whose intrinsics the device solver can free at once
 

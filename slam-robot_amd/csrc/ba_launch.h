@@ -43,6 +43,9 @@ constexpr int kUlStamp = 64 + 2 * kTraceK * 16;
 // k_schur per-segment stamps (SG_STAMP=1): 8 words per segment from kSegStamp (tools/schur_seg_stamps.py)
 constexpr int kSegStamp = kUlStamp + 16;
 constexpr int kSegStampMax = 1024;
+// k_update_lin's stamps of wave 1 of the mid-grid workgroup (8 words, laid out as one of kUlStamp's groups)
+constexpr int kUlStamp1 = kSegStamp + 8 * kSegStampMax;
+constexpr int kStampWords = kUlStamp1 + 8;
 
 // ---- ba_sweep.hip
 void LaunchLinearizeK(int waves, int grid, hipStream_t s, const Dev& d);

@@ -114,6 +114,12 @@ struct LinChunk {
   int32_t u0;         // its first k_point_update work unit (one per round; one for a wide chunk)
 };
 
+// Launch outputs that only a later launch reads, stored write-through (wt_store.h): Dev::wt bits, SG_WT_STORES.
+constexpr int kWtJ = 1;       // the J records (jstore / jstore_zero: k_linearize, k_update_lin)
+constexpr int kWtCam = 2;     // the per-chunk camera partials (lin_combine_waves)
+constexpr int kWtSchur = 4;   // k_schur's segment slabs (schur_store)
+constexpr int kWtStoresDefault = kWtJ | kWtCam | kWtSchur;
+
 // ---- the reduced-camera solves (ba_chol.hip): the sizes the Cholesky choice is made by
 constexpr int kCholWS = 128;           // k_cholesky_window: LDS window columns
 constexpr int kJendSh = 512;           // panel band ends cached in LDS (n <= 8192)

@@ -31,6 +31,7 @@ struct LoadKnobs {
   bool chol_split = true;     // SG_CHOL_SPLIT=0: no dissected band
   bool chol_sep7 = false;     // SG_CHOL_SEP=7: the fixed 7-row separator
   bool stamp = false;         // SG_STAMP=1: cycle stamps
+  int wt_stores = kWtStoresDefault;   // SG_WT_STORES: kWt* bits (ba_layout.h), launch outputs stored write-through
 };
 
 // Camera blocks and the device order of points and observations.

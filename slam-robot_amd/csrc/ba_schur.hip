@@ -523,7 +523,7 @@ __global__ __launch_bounds__(kSchurThreads) void k_schur(Dev d, int fin) {
     mfma_drain();
     switch (cw) {
 #define SG_SCHUR_CASE(W) \
-      case W: schur_store<W>(acc, accr, slab, sg.ntw, lane); break;
+      case W: schur_store<W>(acc, accr, slab, sg.ntw, lane, (d.wt & kWtSchur) != 0); break;
       SG_SCHUR_CASE(0) SG_SCHUR_CASE(1) SG_SCHUR_CASE(2) SG_SCHUR_CASE(3)
 #if SG_SCHUR_CW > 4
       SG_SCHUR_CASE(4) SG_SCHUR_CASE(5) SG_SCHUR_CASE(6) SG_SCHUR_CASE(7)

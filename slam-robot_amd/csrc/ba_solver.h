@@ -114,6 +114,7 @@ class BaSolver {
   // tests: issue the communicator's collectives on one rank too (SG_COMM_FORCE=1: RCCL with one rank is a copy)
   bool comm_force_ = getenv("SG_COMM_FORCE") && atoi(getenv("SG_COMM_FORCE")) == 1;
   bool stamp_on_ = false;
+  int wt_stores_ = 0;                   // Dev::wt of the last full load (SG_WT_STORES)
   int ncu_ = 256;                       // compute units (Schur segment count), queried once
   size_t tile_lds_set_ = 0;             // dynamic LDS last granted to k_chol_tiles
   size_t gchol_lds_max_ = 0;            // dynamic LDS granted to k_cholesky_global

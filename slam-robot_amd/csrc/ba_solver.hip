@@ -145,6 +145,7 @@ static LoadKnobs ReadLoadKnobs() {
   k.chol_split = !is("SG_CHOL_SPLIT", 0);
   k.chol_sep7 = is("SG_CHOL_SEP", kTB - 1);
   k.stamp = getenv("SG_STAMP") && getenv("SG_STAMP")[0] == '1';
+  if (const char* e = getenv("SG_WT_STORES")) k.wt_stores = atoi(e) & (kWtJ | kWtCam | kWtSchur);
   return k;
 }
 
@@ -427,8 +428,9 @@ void BaSolver::Load(const sg_problem& p) {
     Yk_.Resize(28 * (size_t)std::max(P_, 1) * ncam_);
     kpart_.Resize((size_t)(NB_ + 1) * ncam_ * 42);
   }
+  wt_stores_ = knobs.wt_stores;
   stamp_on_ = knobs.stamp;
-  if (stamp_on_) stamps_.Resize(kSegStamp + 8 * kSegStampMax);
+  if (stamp_on_) stamps_.Resize(kStampWords);
   lap("resize");
   ResetState(s);
   if (host_timing) DevMark(s, 3);
@@ -708,6 +710,7 @@ Dev BaSolver::MakeDev() {
   d.xc = S_.ptr + (size_t)n_ * n_;
   d.work = work_.ptr;
   d.stamps = stamp_on_ ? stamps_.ptr : nullptr;
+  d.wt = wt_stores_;
   d.fd_pair = fd_pair_.ptr;
   d.obs_pnt = obs_pnt_.ptr;
   d.lchunks = lchunks_d_.ptr;
@@ -1260,6 +1263,7 @@ void BaSolver::Info(sg_ba_info* o) const {
   o->lin_waves = wk_.lin_waves;
   o->cholesky_separator = chol_.tiles && chol_.nd > 0 ? chol_.ns : 0;
   o->cholesky_stile = chol_stile_last_ ? 1 : 0;
+  o->wt_stores = wt_stores_;
 }
 
 double BaSolver::ReprojectMap(sg_map* m) {

@@ -42,26 +42,31 @@ __device__ __forceinline__ double pt_sum(const double* pa, int v) {
 // The chunk's camera partial (the waves' window accumulators summed in wave order) into its cam_slab slot, and
 // wave 1's six chunk scalars into wave 0's (sums in wave order, gmax a maximum).  Every thread of the
 // workgroup calls it (a workgroup barrier).
+// wt (Dev::wt & kWtCam): the slab as write-through stores (wt_store.h); k_cam_reduce, a later launch, is its reader.
 template <int kW>
 __device__ __forceinline__ void lin_combine_waves(double* slab, double (*camacc_w)[kLinNbMax * kCamV], int ncv,
-                                                  double* wscal, int wv, int lane, double& s0, double& s1,
+                                                  double* wscal, int wv, int lane, bool wt, double& s0, double& s1,
                                                   double& s2, double& s3, double& s4, double& gmax) {
+  auto put = [&](int i, double v) {
+    if (wt) st_wt(slab + i, v);
+    else slab[i] = v;
+  };
   if (kW == 1) {
-    for (int i = lane; i < ncv; i += kLinThreads) slab[i] = camacc_w[0][i];
+    for (int i = lane; i < ncv; i += kLinThreads) put(i, camacc_w[0][i]);
     return;
   }
   if (wv == 1 && lane == 0) {
     wscal[0] = s0; wscal[1] = s1; wscal[2] = s2; wscal[3] = s3; wscal[4] = s4; wscal[5] = gmax;
   }
   lds_barrier();
-  for (int i = threadIdx.x; i < ncv; i += kLinThreads * kW) slab[i] = camacc_w[0][i] + camacc_w[kW - 1][i];
+  for (int i = threadIdx.x; i < ncv; i += kLinThreads * kW) put(i, camacc_w[0][i] + camacc_w[kW - 1][i]);
   if (wv == 0) {
     s0 += wscal[0]; s1 += wscal[1]; s2 += wscal[2]; s3 += wscal[3]; s4 += wscal[4];
     gmax = fmax(gmax, wscal[5]);
   }
 }
 
-template <int kW>
+template <int kW, bool kJWt>
 __global__ __launch_bounds__(kLinThreads * kW) SG_LIN_ATTR void k_linearize(Dev d) {
   const LmState* st = d.st;
   if (st->done || !st->need_lin) return;
@@ -140,7 +145,7 @@ __global__ __launch_bounds__(kLinThreads * kW) SG_LIN_ATTR void k_linearize(Dev 
         } else if (first) {
           lsum[1][lane] += c;
         }
-        jstore_zero(d.J[cur], o);
+        jstore_zero<kJWt>(d.J[cur], o);
       } else {
         cost += c;
         const int b = meta_block(m);
@@ -153,7 +158,7 @@ __global__ __launch_bounds__(kLinThreads * kW) SG_LIN_ATTR void k_linearize(Dev 
         }
         // the record keeps J~p whatever the point's freedom (the translation columns come from it); the point
         // terms below use it only for a free point
-        jstore(d.J[cur], o, rr, Jc, Jp);
+        jstore<kJWt>(d.J[cur], o, rr, Jc, Jp);
         if (pf) {
           double* pa = pacc + (p - Rc.p0) * 14 * kPtCopies;
 #pragma unroll
@@ -222,8 +227,8 @@ __global__ __launch_bounds__(kLinThreads * kW) SG_LIN_ATTR void k_linearize(Dev 
   double ffail = wave_sum_full(lsum[2][lane]);
   double xn2 = wave_sum_full(lsum[3][lane]);
   gmax = wave_max_full(gmax);
-  lin_combine_waves<kW>(d.cam_slab[cur] + ch.cam_off, camacc_w, ncv, wscal, wv, lane, cost, fail, fixed, ffail,
-                        xn2, gmax);
+  lin_combine_waves<kW>(d.cam_slab[cur] + ch.cam_off, camacc_w, ncv, wscal, wv, lane, (d.wt & kWtCam) != 0, cost, fail,
+                        fixed, ffail, xn2, gmax);
   if (wv == 0 && lane == 0) {
     double* sc = d.lin_scal[cur] + blockIdx.x;   // structure of arrays: slot j at [j * nlin + chunk]
     const size_t ns = d.nlin;
@@ -559,6 +564,7 @@ __global__ __launch_bounds__(kLinThreads) void k_point_update(Dev d) {
 // One lane's observation of round R: the model term of the current linearization (ob, from pass 1), then
 // project.h + analytic Jacobian + Cauchy corrector at the candidate (k_linearize's body at x[nxt]): the J
 // record into slot nxt, the candidate's point and camera terms into LDS, its cost.
+template <bool kJWt>
 __device__ __forceinline__ void ul_obs(const Dev& d, const LinRound& R, const LinChunk& ch, int lane, int nxt,
                                        const PuObs& ob, const double* xps, const double* Xns, double* pacc,
                                        double* camacc, double (*lsum)[kLinThreads], double& model, double& cost,
@@ -592,7 +598,7 @@ __device__ __forceinline__ void ul_obs(const Dev& d, const LinRound& R, const Li
   }
   if (!ok || fx) {
     if (!ok) lsum[fx ? 1 : 0][lane] += 1.0;   // (a fixed observation's cost counts at iteration 0 only)
-    jstore_zero(d.J[nxt], o);
+    jstore_zero<kJWt>(d.J[nxt], o);
     return;
   }
   cost += c;
@@ -605,7 +611,8 @@ __device__ __forceinline__ void ul_obs(const Dev& d, const LinRound& R, const Li
     if (!(m & kMetaRot)) { Jc[0] = Jc[1] = Jc[2] = Jc[6] = Jc[7] = Jc[8] = 0.0; }
     if (!(m & kMetaTrans)) { Jc[3] = Jc[4] = Jc[5] = Jc[9] = Jc[10] = Jc[11] = 0.0; }
   }
-  jstore(d.J[nxt], o, rr, Jc, Jp);   // (J~p kept whatever the point's freedom; the point terms take it if free)
+  // (J~p kept whatever the point's freedom; the point terms take it if free)
+  jstore<kJWt>(d.J[nxt], o, rr, Jc, Jp);
 #ifndef SG_X_NOPATOM   // timing-only experiment build (results wrong): no point-block LDS atomics
   if (pf) {
     double* pa = pacc + lp * 14 * kPtCopies;
@@ -653,7 +660,7 @@ __device__ __forceinline__ void ul_points(const Dev& d, int p0, int p1, int lane
   if (d.pfree[pp]) gmax = fmax(gmax, fmax(fmax(fabs(g[0]), fabs(g[1])), fmax(fabs(g[2]), fabs(g[3]))));
 }
 
-template <bool kStamp, int kW>
+template <bool kStamp, int kW, bool kJWt>
 __global__ __launch_bounds__(kLinThreads * kW) SG_LIN_ATTR void k_update_lin(Dev d) {
   const LmState* st = d.st;
   const int done = st->done;
@@ -689,15 +696,17 @@ __global__ __launch_bounds__(kLinThreads * kW) SG_LIN_ATTR void k_update_lin(Dev
   double cost = 0.0, gmax = 0.0;
   double model = 0.0, candcost = 0.0, candfail = 0.0, step2 = 0.0, candx2 = 0.0;
   // SG_STAMP=1 (the kStamp build): lane 0 of the mid-grid and the last workgroup time their steps
-  // (d.stamps[kUlStamp + 8 w + k])
-  const int stw = !kStamp || !d.stamps || threadIdx.x != 0 ? -1
+  // (d.stamps[kUlStamp + 8 w + k]), and lane 0 of the mid-grid workgroup's wave 1 (d.stamps[kUlStamp1 + k])
+  const int stw = !kStamp || !d.stamps || lane != 0 ? -1
+                  : wv == 1 ? (blockIdx.x == gridDim.x / 2 ? 2 : -1)
                   : blockIdx.x == gridDim.x / 2 ? 0 : blockIdx.x == gridDim.x - 1 ? 1 : -1;
+  unsigned long long* const stp = !kStamp || stw < 0 ? nullptr : d.stamps + (stw == 2 ? kUlStamp1 : kUlStamp + 8 * stw);
   unsigned long long tl = 0;
   auto ul_stamp = [&](int k) {
     if (stw < 0) return;
     unsigned long long t;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
-    if (k >= 0) d.stamps[kUlStamp + 8 * stw + k] += t - tl;
+    if (k >= 0) stp[k] += t - tl;
     tl = t;
   };
   ul_stamp(-1);
@@ -712,7 +721,7 @@ __global__ __launch_bounds__(kLinThreads * kW) SG_LIN_ATTR void k_update_lin(Dev
       pu_pass2(d, R.p0, R.p1, lane, cur, nxt, ua, xps, Xns, step2, candx2);
       lds_fence_wave();
       ul_stamp(1);
-      ul_obs(d, R, ch, lane, nxt, ob, xps, Xns, pacc, camacc, lsum, model, cost, candcost, candfail);
+      ul_obs<kJWt>(d, R, ch, lane, nxt, ob, xps, Xns, pacc, camacc, lsum, model, cost, candcost, candfail);
       lds_fence_wave();
       ul_stamp(2);
       ul_points(d, R.p0, R.p1, lane, nxt, pacc, gmax);
@@ -732,7 +741,7 @@ __global__ __launch_bounds__(kLinThreads * kW) SG_LIN_ATTR void k_update_lin(Dev
       const LinRound R = d.lrounds[r];
       PuObs ob;
       pu_pass1(d, cur, R, lane, nullptr, ob);
-      ul_obs(d, R, ch, lane, nxt, ob, xps, Xns, pacc, camacc, lsum, model, cost, candcost, candfail);
+      ul_obs<kJWt>(d, R, ch, lane, nxt, ob, xps, Xns, pacc, camacc, lsum, model, cost, candcost, candfail);
     }
     lds_fence_wave();
     ul_points(d, ch.p0, ch.p1, lane, nxt, pacc, gmax);
@@ -752,8 +761,8 @@ __global__ __launch_bounds__(kLinThreads * kW) SG_LIN_ATTR void k_update_lin(Dev
   gmax = wave_max_full(gmax);
   // the same combine as k_linearize's (its fixed and |X|^2 sums are zero here)
   double fixed = 0.0, xn2 = 0.0;
-  lin_combine_waves<kW>(d.cam_slab[nxt] + ch.cam_off, camacc_w, ncv, wscal, wv, lane, cost, fail, fixed, ffail,
-                        xn2, gmax);
+  lin_combine_waves<kW>(d.cam_slab[nxt] + ch.cam_off, camacc_w, ncv, wscal, wv, lane, (d.wt & kWtCam) != 0, cost, fail,
+                        fixed, ffail, xn2, gmax);
   if (wv == 0 && lane == 0) {
     {
       double* su = d.chunk_scal + blockIdx.x;   // structure of arrays: slot j at [j * npu + chunk]
@@ -777,7 +786,7 @@ __global__ __launch_bounds__(kLinThreads * kW) SG_LIN_ATTR void k_update_lin(Dev
     sc[kGmax * ns] = gmax;
   }
   ul_stamp(5);
-  if (stw >= 0) d.stamps[kUlStamp + 8 * stw + 6] += 1;   // launches stamped
+  if (stw >= 0) stp[6] += 1;   // launches stamped
 }
 
 
@@ -951,25 +960,36 @@ __global__ __launch_bounds__(64) void k_reproject_reduce(const double* partial, 
 // ------------------------------------------------------------------------------------------------
 // host launchers (ba_launch.h)
 
-void LaunchLinearizeK(int waves, int grid, hipStream_t s, const Dev& d) {
+// (the J records' store form is an instance, Dev::wt & kWtJ: jstore, ba_device.h)
+template <bool kJWt>
+static void LaunchLinearizeW(int waves, int grid, hipStream_t s, const Dev& d) {
   if (waves == 2)
-    hipLaunchKernelGGL(k_linearize<2>, dim3(grid), dim3(2 * kLinThreads), 0, s, d);
+    hipLaunchKernelGGL((k_linearize<2, kJWt>), dim3(grid), dim3(2 * kLinThreads), 0, s, d);
   else
-    hipLaunchKernelGGL(k_linearize<1>, dim3(grid), dim3(kLinThreads), 0, s, d);
+    hipLaunchKernelGGL((k_linearize<1, kJWt>), dim3(grid), dim3(kLinThreads), 0, s, d);
+}
+void LaunchLinearizeK(int waves, int grid, hipStream_t s, const Dev& d) {
+  if (d.wt & kWtJ) LaunchLinearizeW<true>(waves, grid, s, d);
+  else LaunchLinearizeW<false>(waves, grid, s, d);
 }
 
-void LaunchUpdateLinK(bool stamp, int waves, int grid, hipStream_t s, const Dev& d) {
+template <bool kJWt>
+static void LaunchUpdateLinW(bool stamp, int waves, int grid, hipStream_t s, const Dev& d) {
   if (waves == 2) {
     if (stamp)
-      hipLaunchKernelGGL((k_update_lin<true, 2>), dim3(grid), dim3(2 * kLinThreads), 0, s, d);
+      hipLaunchKernelGGL((k_update_lin<true, 2, kJWt>), dim3(grid), dim3(2 * kLinThreads), 0, s, d);
     else
-      hipLaunchKernelGGL((k_update_lin<false, 2>), dim3(grid), dim3(2 * kLinThreads), 0, s, d);
+      hipLaunchKernelGGL((k_update_lin<false, 2, kJWt>), dim3(grid), dim3(2 * kLinThreads), 0, s, d);
   } else {
     if (stamp)
-      hipLaunchKernelGGL((k_update_lin<true, 1>), dim3(grid), dim3(kLinThreads), 0, s, d);
+      hipLaunchKernelGGL((k_update_lin<true, 1, kJWt>), dim3(grid), dim3(kLinThreads), 0, s, d);
     else
-      hipLaunchKernelGGL((k_update_lin<false, 1>), dim3(grid), dim3(kLinThreads), 0, s, d);
+      hipLaunchKernelGGL((k_update_lin<false, 1, kJWt>), dim3(grid), dim3(kLinThreads), 0, s, d);
   }
+}
+void LaunchUpdateLinK(bool stamp, int waves, int grid, hipStream_t s, const Dev& d) {
+  if (d.wt & kWtJ) LaunchUpdateLinW<true>(stamp, waves, grid, s, d);
+  else LaunchUpdateLinW<false>(stamp, waves, grid, s, d);
 }
 
 void LaunchPointUpdateK(int grid, hipStream_t s, const Dev& d) {

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ba_kernels.h"
+#include "wt_store.h"
 
 namespace sg {
 
@@ -96,9 +97,11 @@ __device__ __forceinline__ void schur_wave_batch(f64x4 (&acc)[kSchurTPW], double
 
 // Slab of a segment: its ntw (ntw + 1) / 2 window tiles (row-major 16x16, column-major upper order), then the
 // rhs of its 16 ntw window columns.  The accumulators must be drained (mfma_drain) first.
+// wt (wave-uniform, Dev::wt & kWtSchur): the tiles as write-through stores (wt_store.h; k_schur reads no slab, the
+// next launch, k_S_reduce, does); the rhs entries, one lane in four, stay plain.
 template <int W>
 __device__ __forceinline__ void schur_store(const f64x4 (&acc)[kSchurTPW], const double (&accr)[kSchurTPW], double* slab,
-                                            int ntw, int lane) {
+                                            int ntw, int lane, bool wt = false) {
   const int ntile = ntw * (ntw + 1) / 2;
 #pragma unroll
   for (int S = 0; S < kSchurTPW; ++S) {
@@ -108,8 +111,13 @@ __device__ __forceinline__ void schur_store(const f64x4 (&acc)[kSchurTPW], const
     if (c >= ntw) continue;
     if (r <= c) {
       double* t = slab + 256 * schur_tile_index(r, c) + lane;   // element (lk + 4 q, li) at 16 lk + li + 64 q
+      if (wt) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) t[64 * q] = -acc[S][q];
+        for (int q = 0; q < 4; ++q) st_wt(t + 64 * q, -acc[S][q]);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) t[64 * q] = -acc[S][q];
+      }
     } else if ((lane & 3) == 0) {
       // E_c^T w (the 4 x 4 x 4 MFMA's D, block b row i column j at lane j + 4 b + 16 i): column 0, window row
       // 16 c + 4 b + i
