@@ -306,6 +306,33 @@ int sg_slam_last_summary(const sg_slam* s, sg_solver_summary* out);
 int sg_slam_solve_frame_poses(sg_slam* s, sg_map* map, const int32_t* frames, int32_t n, double range,
                               int32_t with_frame_distance, int32_t* solved /*[n]*/,
                               sg_solver_summary* summaries /*[n], may be NULL*/);
+/* Structure-only bundle adjustment, the dual of sg_slam_solve_frame_poses: given the frames as they are, where
+ * are these landmarks?  Its first customers are the points Matcher::Track seeds at a guessed depth
+ * (Unproject(..., 2000), localmap.cpp:106-110), which the window solve does not touch while they carry
+ * NO_BASELINE | NO_OBSERVATIONS.  Each listed point p is solved on its own against the map as it is at entry:
+ *   - Residuals: one ReprojectionError (slam.cpp:60-84, 285-294) with CauchyLoss(range) per observation of p with
+ *     obs_disabled == 0, in map order, from whatever frame.
+ *   - Point flags are NOT consulted and not written.  This differs from Slam::SetupProblem's filter (slam.cpp:280-283
+ *     skips every point that is not slam-usable): the caller runs Clean / CheckFlags afterwards as before.
+ *   - Parameter blocks: X[4p .. 4p+3] free without a parameterization (4 unknowns, as slam.cpp leaves it); every
+ *     frame and every intrinsics block constant; no FrameDistance; fixed_cost is 0.
+ *   - Solver: the handle's sg_solver_options (sg_slam_set_options) on the Ceres 1.8 LM of sg_ba_solve: Jacobi
+ *     scaling, the clamped LM diagonal, a 4x4 Cholesky of the damped scaled system (a non-positive pivot makes an
+ *     invalid step), the model cost change from the stored system, the same step decision.  Every point has its
+ *     own trust region.  All points of a call run in one device launch, eight lanes each.
+ *   - A point with fewer than 2 enabled observations is not solved: solved[i] = 0, SG_DID_NOT_RUN, X untouched
+ *     (decided before anything is launched).
+ *   - A point whose solve ends with ok = 0 (a start behind one of its cameras, or
+ *     max_num_consecutive_invalid_steps invalid steps in a row: SG_NUMERICAL_FAILURE) also keeps its X and gets
+ *     solved[i] = 0.  Otherwise the four doubles are written as the solver leaves them, not renormalized (as Ceres
+ *     does through the raw pointer); nothing else of the map is written.
+ *   - A point index out of range or listed twice: SG_EINVAL, nothing changed.  n < 0 or a null s or map:
+ *     SG_EINVAL.  n == 0 returns SG_OK before the handle or the device is touched.
+ * summaries (may be NULL) receives each point's summary.  sg_slam_iterations grows by the num_iterations of the
+ * points that ran, and sg_slam_error / sg_slam_last_summary take the values of the last listed point that ran (the
+ * convention of sg_slam_solve_frame_poses).  No communicator is involved: rank-local on a sharded handle. */
+int sg_slam_solve_points(sg_slam* s, sg_map* map, const int32_t* points, int32_t n, double range,
+                         int32_t* solved /*[n]*/, sg_solver_summary* summaries /*[n], may be NULL*/);
 
 /* ------------------------------------------------------------------------------------------------
  * Front end: HessianTracker (hessian.h:9-270) and the forward/backward matching step of Matcher

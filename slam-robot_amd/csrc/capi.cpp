@@ -9,6 +9,7 @@
 #include <cstring>
 #include <memory>
 
+#include "ba_points.h"
 #include "ba_pose.h"
 #include "ba_solver.h"
 #include "comm.h"
@@ -27,6 +28,7 @@ struct sg_slam {
   std::unique_ptr<sg::BaSolver> solver;
   std::unique_ptr<sg::MapOps> mapops;   // created on first use
   std::unique_ptr<sg::PoseSolver> pose;  // created on first use (sg_slam_solve_frame_poses)
+  std::unique_ptr<sg::PointSolver> points;   // created on first use (sg_slam_solve_points)
   sg_device_options dev;
   sg_solver_options options;
   int32_t iterations = 0;    // Slam::iterations_ (slam.cpp:517)
@@ -397,6 +399,45 @@ int sg_slam_debug_pose_kernel_ms(sg_slam* s, double* ms) {
   SG_CAPI_BEGIN
   SG_REQUIRE(s && ms, SG_EINVAL, "null argument");
   *ms = PoseSolverOf(s).last_kernel_ms();
+  SG_CAPI_END
+}
+
+static sg::PointSolver& PointSolverOf(sg_slam* s) {
+  if (!s->points) s->points.reset(new sg::PointSolver(s->dev, s->solver->stream()));   // one stream per Slam object
+  return *s->points;
+}
+
+int sg_slam_solve_points(sg_slam* s, sg_map* map, const int32_t* points, int32_t n, double range, int32_t* solved,
+                         sg_solver_summary* summaries) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s && map, SG_EINVAL, "null argument");
+  SG_REQUIRE(n >= 0, SG_EINVAL, "negative point count");
+  if (n == 0) return SG_OK;   // nothing to solve: neither the handle nor the device is touched
+  SG_REQUIRE(points && solved, SG_EINVAL, "null point list or result array");
+  sg::PointSolver& ps = PointSolverOf(s);
+  ps.Solve(map, points, n, range, s->options, solved, summaries);
+  // Slam::Run's bookkeeping (slam.cpp:517-518) over the points that ran, in list order
+  for (const sg_solver_summary& sum : ps.summaries()) {
+    if (sum.termination_type == SG_DID_NOT_RUN) continue;
+    s->iterations += sum.num_iterations;
+    s->error = sum.final_cost;
+    s->last = sum;
+  }
+  SG_CAPI_END
+}
+
+// Diagnostics (not in the public header): HIP-event time of the k_point_lm launch (tools/points_bench.py).
+int sg_slam_debug_points_timing(sg_slam* s, int32_t enable) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s, SG_EINVAL, "null handle");
+  PointSolverOf(s).SetTiming(enable != 0);
+  SG_CAPI_END
+}
+
+int sg_slam_debug_points_kernel_ms(sg_slam* s, double* ms) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s && ms, SG_EINVAL, "null argument");
+  *ms = PointSolverOf(s).last_kernel_ms();
   SG_CAPI_END
 }
 

@@ -275,6 +275,25 @@ class Slam:
         """Summary dicts of the last SolveFramePoses call, one per listed frame."""
         return list(getattr(self, "_pose_summaries", []))
 
+    def SolvePoints(self, m: MapArrays, points, range_: float) -> list:
+        """Structure-only bundle adjustment (sg_slam_solve_points): each listed point's location against the map's
+        frames as they are, all points in one device launch.  Point flags are not consulted.  Updates m.X of the
+        solved points in place and returns one bool per listed point; point_summaries() has their summaries."""
+        pts = np.ascontiguousarray(points, dtype=np.int32).reshape(-1)
+        n = len(pts)
+        solved = np.zeros(n, dtype=np.int32)
+        sums = (SgSolverSummary * max(n, 1))()
+        ms = m.struct()
+        check(self.lib.sg_slam_solve_points(self.h, C.byref(ms), pts.ctypes.data_as(C.POINTER(C.c_int32)), n, range_,
+                                            solved.ctypes.data_as(C.POINTER(C.c_int32)), sums),
+              "Slam::SolvePoints")
+        self._point_summaries = [sums[i].as_dict() for i in range(n)]
+        return [bool(v) for v in solved]
+
+    def point_summaries(self) -> list:
+        """Summary dicts of the last SolvePoints call, one per listed point."""
+        return list(getattr(self, "_point_summaries", []))
+
     def ReprojectMap(self, m: MapArrays) -> float:
         mean = C.c_double()
         ms = m.struct()

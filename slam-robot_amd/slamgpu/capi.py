@@ -318,6 +318,8 @@ SYMBOLS = {
     "sg_slam_set_options": (C.c_int, [C.c_void_p, C.POINTER(SgSolverOptions)]),
     "sg_slam_solve_frame_poses": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32, C.c_double, C.c_int32, _ip,
                                             C.POINTER(SgSolverSummary)]),
+    "sg_slam_solve_points": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32, C.c_double, _ip,
+                                       C.POINTER(SgSolverSummary)]),
     "sg_frontend_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SgTrackerOptions), C.POINTER(SgDeviceOptions)]),
     "sg_frontend_destroy": (None, [C.c_void_p]),
     "sg_frontend_track": (C.c_int, [C.c_void_p, _u8p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
