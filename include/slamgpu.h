@@ -334,6 +334,67 @@ int sg_slam_solve_frame_poses(sg_slam* s, sg_map* map, const int32_t* frames, in
 int sg_slam_solve_points(sg_slam* s, sg_map* map, const int32_t* points, int32_t n, double range,
                          int32_t* solved /*[n]*/, sg_solver_summary* summaries /*[n], may be NULL*/);
 
+/* Linear multi-view triangulation: given the frames as they are, where are these landmarks, from their
+ * observations alone?  ("Triangulate points for initialization after there are known poses", main.cpp:3.)  Unlike
+ * sg_slam_solve_points it needs no start: the location at entry is not read, so a point seeded at a guessed depth
+ * (Unproject(..., 2000)), or one whose start projects behind a camera, gets the closed-form answer.  Per listed
+ * point, from its observations with obs_disabled == 0, in map order, from whatever frame (point flags are not
+ * consulted and not written):
+ *   1. each pixel is undistorted to plane coordinates (a, b) by Newton on the radius (the inverse of
+ *      Camera::PlaneToPixel, localmap.h:38-56, to rounding; not PixelToPlane's three fixed-point rounds);
+ *   2. a local frame for conditioning: origin c0 = the first observation's camera centre, unit L = the rms distance
+ *      of the observing centres from c0.  L == 0: SG_TRI_NO_BASELINE;
+ *   3. two rows [n, -n . c_i] per observation, n = a r3 - r1 and n = b r3 - r2 (r1..r3 the rows of the frame's
+ *      rotation, c_i = (t_i - c0) / L), summed into the symmetric 4x4 M;
+ *   4. y = the unit eigenvector of M's smallest eigenvalue (cyclic Jacobi), eigenvalues l0 <= l1 <= l2 <= l3.
+ *      l1 - l0 <= 1e-12 l3, or any non-finite value: SG_TRI_DEGENERATE;
+ *   5. X = (L y.xyz + c0 y.w, y.w), with the sign that makes X.w >= 0 (X.w == 0: the sign that puts the point in
+ *      front of the first observation's camera), scaled to unit 4-norm as Frame::Unproject leaves it
+ *      (localmap.cpp:35).  The reference's own behind-camera test p.z < 0.001 X.w (project.h:27) accepts a point
+ *      behind every camera when W < 0, both sides being negative; with W >= 0 fixed first it is the physical test;
+ *   6. at X: behind = the observations the projection rejects (project.h:27), max_error_px = the largest
+ *      reprojection error of the others, parallax = the largest angle at the point between the directions to an
+ *      observing centre and to the first one;
+ *   7. the status is the first of sg_tri_status' rules that applies, in the order of the enum below.
+ * solved[i] = 1 and X is written for exactly the SG_TRI_OK points; every other point keeps its X.  With refine != 0
+ * the SG_TRI_OK points are then polished by sg_slam_solve_points' solver (the handle's sg_solver_options,
+ * CauchyLoss(range)) from the triangulated location, on the device, without a host round trip: the written X is
+ * that solve's when it ends with ok = 1 and the triangulated one otherwise (solved[i] stays 1).  Nothing else of
+ * the map is written, and a failing call writes nothing.
+ *   - A point index out of range or listed twice: SG_EINVAL.  n < 0 or a null s, map or options: SG_EINVAL.
+ *     n == 0 returns SG_OK before the handle or the device is touched.
+ * results (may be NULL) receives each point's sg_triangulate_result, summaries (may be NULL) the polish's summary
+ * (SG_DID_NOT_RUN for every point the polish did not run on).  sg_slam_iterations, sg_slam_error and
+ * sg_slam_last_summary move only by the polish, by the convention of sg_slam_solve_points. */
+enum sg_tri_status {
+  SG_TRI_OK = 0,
+  SG_TRI_DID_NOT_RUN = 1,    /* fewer than 2 enabled observations (decided before anything is launched) */
+  SG_TRI_NO_BASELINE = 2,    /* every observation from one camera centre */
+  SG_TRI_DEGENERATE = 3,     /* the null direction of M is not determined, or a non-finite value */
+  SG_TRI_BEHIND = 4,         /* behind at least one of its cameras */
+  SG_TRI_LOW_PARALLAX = 5,   /* parallax < min_parallax */
+  SG_TRI_HIGH_ERROR = 6      /* max_error_px > the max_error_px option */
+};
+
+typedef struct sg_triangulate_options {
+  double min_parallax;   /* rad; 0 = no gate */
+  double max_error_px;   /* px;  0 = no gate */
+  int32_t refine;        /* != 0: k_point_lm from the triangulated location */
+  double range;          /* CauchyLoss range of the polish (ignored when refine == 0) */
+} sg_triangulate_options;
+
+typedef struct sg_triangulate_result {
+  int32_t status, num_obs;                  /* enum sg_tri_status; enabled observations */
+  double parallax, max_error_px, rel_gap;   /* rad; px; (l1 - l0) / l3 */
+  double X[4];                              /* triangulated location (before the polish); zeros unless computed */
+} sg_triangulate_result;
+
+void sg_triangulate_options_default(sg_triangulate_options* o);   /* gates off, refine = 0, range = 2.0 */
+int sg_slam_triangulate_points(sg_slam* s, sg_map* map, const int32_t* points, int32_t n,
+                               const sg_triangulate_options* options, int32_t* solved /*[n]*/,
+                               sg_triangulate_result* results /*[n], may be NULL*/,
+                               sg_solver_summary* summaries /*[n], may be NULL*/);
+
 /* ------------------------------------------------------------------------------------------------
  * Front end: HessianTracker (hessian.h:9-270) and the forward/backward matching step of Matcher
  * (matcher.cpp:173-206 TrackFeature, 247-251 the 3 -> 6 level retry).  A tracker holds `max_images`

@@ -75,6 +75,13 @@ __device__ __forceinline__ double sum8_dpp(double v) {
   v += dpp_d<0x141>(v);
   return v;
 }
+// The same three steps for the maximum over the group (fmax is exact: every lane gets the same bits).
+__device__ __forceinline__ double max8_dpp(double v) {
+  v = fmax(v, dpp_d<0xB1>(v));
+  v = fmax(v, dpp_d<0x4E>(v));
+  v = fmax(v, dpp_d<0x141>(v));
+  return v;
+}
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m));

@@ -1,5 +1,6 @@
 // ba_points.h — structure-only bundle adjustment (sg_slam_solve_points): host driver of k_point_lm; see
-// ba_points.hip.
+// ba_points.hip.  The same driver runs sg_slam_triangulate_points (k_point_triangulate, ba_triangulate.hip), whose
+// polish is k_point_lm on the same upload.
 #ifndef SG_BA_POINTS_H_
 #define SG_BA_POINTS_H_
 
@@ -11,6 +12,13 @@
 #include "points_plan.h"
 
 namespace sg {
+
+constexpr int kPointThreads = 256;
+// Lanes per point.  8 sits at the mean track length of the SLAM maps (7.6 observations per point at C2, 10 at
+// C5), and a wave waits for the slowest of 64 / 8 = 8 points, not of 64.  sum8_dpp is written for this size.
+constexpr int kPointGroup = 8;
+constexpr int kPointsPerBlock = kPointThreads / kPointGroup;
+static_assert(kPointGroup == 8, "sum8_dpp: quad perms and the half-row mirror span 8 lanes");
 
 // What k_point_lm writes per listed point that ran: the solved location and the minimizer's summary fields.
 struct PointOut {
@@ -33,11 +41,29 @@ class PointSolver {
   void Solve(sg_map* m, const int32_t* points, int32_t n, double range, const sg_solver_options& o, int32_t* solved,
              sg_solver_summary* summaries);
   const std::vector<sg_solver_summary>& summaries() const { return sums_; }
-  // Development aid (tools/points_bench.py): HIP-event time of the k_point_lm launch of the calls that follow.
+  // sg_slam_triangulate_points (ba_triangulate.hip): k_point_triangulate on the listed points and, with
+  // t.refine, k_point_lm from the triangulated locations on the same stream (one upload, two launches, one
+  // download).  Writes the locations of the SG_TRI_OK points into m, solved[n] and (if not null) results[n] and
+  // summaries[n]; summaries() holds the polish's summaries (SG_DID_NOT_RUN where it did not run).
+  void Triangulate(sg_map* m, const int32_t* points, int32_t n, const sg_triangulate_options& t,
+                   const sg_solver_options& o, int32_t* solved, sg_triangulate_result* results,
+                   sg_solver_summary* summaries);
+  const std::vector<sg_triangulate_result>& triangulation_results() const { return tri_; }
+  // Development aid (tools/points_bench.py, tools/triangulate_bench.py): HIP-event time of the kernel launches of
+  // the calls that follow.
   void SetTiming(bool on) { timing_ = on; }
   double last_kernel_ms() const { return kernel_ms_; }
 
  private:
+  // The pieces Solve and Triangulate share.  Upload: plan_ to the device (out_ sized for n points).  LaunchLm:
+  // k_point_lm on the uploaded plan.  TimeBegin / TimeEnd: the HIP events around a call's launches.  Summarize:
+  // out_h_[i] into sums_[i].
+  void Upload(int32_t n);
+  void LaunchLm(int32_t n, double range, const sg_solver_options& o);
+  void TimeBegin();
+  void TimeEnd();
+  void Summarize(int32_t i);
+
   sg_device_options dev_;
   hipStream_t stream_ = nullptr;
   bool own_stream_ = false;
@@ -51,6 +77,8 @@ class PointSolver {
   DBuf<PointOut> out_;
   std::vector<PointOut> out_h_;
   std::vector<sg_solver_summary> sums_;
+  DBuf<sg_triangulate_result> tri_d_;
+  std::vector<sg_triangulate_result> tri_, tri_h_;
   bool timing_ = false;
   double kernel_ms_ = 0.0;
   hipEvent_t ev_[2] = {nullptr, nullptr};

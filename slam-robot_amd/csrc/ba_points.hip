@@ -27,12 +27,6 @@ namespace sg {
 
 namespace {
 
-constexpr int kPointThreads = 256;
-// Lanes per point.  8 sits at the mean track length of the SLAM maps (7.6 observations per point at C2, 10 at
-// C5), and a wave waits for the slowest of 64 / 8 = 8 points, not of 64.  sum8_dpp is written for this size.
-constexpr int kPointGroup = 8;
-constexpr int kPointsPerBlock = kPointThreads / kPointGroup;
-static_assert(kPointGroup == 8, "sum8_dpp: quad perms and the half-row mirror span 8 lanes");
 // A linearization's sums: the 10 upper entries of J^T J (u4 order) | J^T r (4) | cost | behind-camera count
 constexpr int kPtNV = 16;
 constexpr int kPG = 10, kPCost = 14, kPFail = 15;
@@ -295,6 +289,71 @@ PointSolver::~PointSolver() {
   if (own_stream_ && stream_) (void)hipStreamDestroy(stream_);
 }
 
+void PointSolver::Upload(int32_t n) {
+  SG_HIP_CHECK(hipSetDevice(dev_.device));
+  io_.Begin();
+  io_.Up(off_, plan_.off);
+  io_.Up(obs_, plan_.obs);
+  io_.Up(frames_, plan_.frames);
+  io_.Up(k_, plan_.k);
+  io_.Up(points_, plan_.points);
+  out_.Resize((size_t)n);
+  io_.FlushUp(stream_);
+}
+
+void PointSolver::LaunchLm(int32_t n, double range, const sg_solver_options& o) {
+  PointArgs a{};
+  a.off = off_.ptr;
+  a.obs = obs_.ptr;
+  a.frames = frames_.ptr;
+  a.k = k_.ptr;
+  a.points = points_.ptr;
+  a.out = out_.ptr;
+  a.b = range * range;
+  a.inv_b = 1.0 / a.b;
+  a.n = n;
+  // the bound of BaSolver::Solve's host loop: every iteration, rejected and invalid steps included
+  const long long cap =
+      (long long)std::max(o.max_num_iterations, 0) * (std::max(o.max_num_consecutive_invalid_steps, 0) + 2) + 16;
+  a.cap = (int32_t)std::min<long long>(cap, INT_MAX);
+  const unsigned grid = (unsigned)((n + kPointsPerBlock - 1) / kPointsPerBlock);
+  hipLaunchKernelGGL(k_point_lm, dim3(grid), dim3(kPointThreads), 0, stream_, a, InitialLmState(o));
+  SG_HIP_CHECK(hipGetLastError());
+}
+
+void PointSolver::TimeBegin() {
+  if (!timing_) return;
+  for (hipEvent_t& e : ev_)
+    if (!e) SG_HIP_CHECK(hipEventCreate(&e));
+  SG_HIP_CHECK(hipEventRecord(ev_[0], stream_));
+}
+
+// (after the call's download: both events have completed)
+void PointSolver::TimeEnd() {
+  if (!timing_) return;
+  float ms = 0.f;
+  SG_HIP_CHECK(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
+  kernel_ms_ = ms;
+}
+
+void PointSolver::Summarize(int32_t i) {
+  const PointOut& r = out_h_[i];
+  SG_REQUIRE(r.finished, SG_EDEVICE, "LM loop did not terminate on the device");
+  sg_solver_summary& su = sums_[i];
+  su.num_iterations = r.num_iterations;
+  su.num_successful_steps = r.n_succ;
+  su.num_unsuccessful_steps = r.n_unsucc;
+  su.num_invalid_steps = r.n_invalid;
+  su.termination_type = r.termination;
+  su.ok = r.ok;
+  su.initial_cost = r.initial_cost;
+  su.final_cost = r.final_cost;
+  su.fixed_cost = 0.0;
+  su.trust_region_radius = r.radius;
+  su.num_lm_iterations = r.lm_iters;
+  su.sync_timeouts = 0;   // nothing to time out on: no hand-off between workgroups
+}
+
 void PointSolver::Solve(sg_map* m, const int32_t* points, int32_t n, double range, const sg_solver_options& o,
                         int32_t* solved, sg_solver_summary* summaries) {
   SG_REQUIRE(m && (n == 0 || (points && solved)), SG_EINVAL, "null argument");
@@ -305,64 +364,16 @@ void PointSolver::Solve(sg_map* m, const int32_t* points, int32_t n, double rang
   for (int i = 0; i < n; ++i) solved[i] = 0;
   kernel_ms_ = 0.0;
   if (plan_.num_run > 0) {
-    SG_HIP_CHECK(hipSetDevice(dev_.device));
-    io_.Begin();
-    io_.Up(off_, plan_.off);
-    io_.Up(obs_, plan_.obs);
-    io_.Up(frames_, plan_.frames);
-    io_.Up(k_, plan_.k);
-    io_.Up(points_, plan_.points);
-    out_.Resize((size_t)n);
-    io_.FlushUp(stream_);
-    PointArgs a{};
-    a.off = off_.ptr;
-    a.obs = obs_.ptr;
-    a.frames = frames_.ptr;
-    a.k = k_.ptr;
-    a.points = points_.ptr;
-    a.out = out_.ptr;
-    a.b = range * range;
-    a.inv_b = 1.0 / a.b;
-    a.n = n;
-    // the bound of BaSolver::Solve's host loop: every iteration, rejected and invalid steps included
-    const long long cap =
-        (long long)std::max(o.max_num_iterations, 0) * (std::max(o.max_num_consecutive_invalid_steps, 0) + 2) + 16;
-    a.cap = (int32_t)std::min<long long>(cap, INT_MAX);
-    if (timing_) {
-      for (hipEvent_t& e : ev_)
-        if (!e) SG_HIP_CHECK(hipEventCreate(&e));
-      SG_HIP_CHECK(hipEventRecord(ev_[0], stream_));
-    }
-    const unsigned grid = (unsigned)((n + kPointsPerBlock - 1) / kPointsPerBlock);
-    hipLaunchKernelGGL(k_point_lm, dim3(grid), dim3(kPointThreads), 0, stream_, a, InitialLmState(o));
-    SG_HIP_CHECK(hipGetLastError());
+    Upload(n);
+    TimeBegin();
+    LaunchLm(n, range, o);
     if (timing_) SG_HIP_CHECK(hipEventRecord(ev_[1], stream_));
     out_h_.resize((size_t)n);
     io_.Down(out_h_.data(), out_.ptr, (size_t)n * sizeof(PointOut));
     io_.FinishDown(stream_);
-    if (timing_) {
-      float ms = 0.f;
-      SG_HIP_CHECK(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
-      kernel_ms_ = ms;
-    }
-    for (int i = 0; i < n; ++i) {
-      if (!plan_.points[i].run) continue;   // (its PointOut was not written)
-      const PointOut& r = out_h_[i];
-      SG_REQUIRE(r.finished, SG_EDEVICE, "LM loop did not terminate on the device");
-      sg_solver_summary& su = sums_[i];
-      su.num_iterations = r.num_iterations;
-      su.num_successful_steps = r.n_succ;
-      su.num_unsuccessful_steps = r.n_unsucc;
-      su.num_invalid_steps = r.n_invalid;
-      su.termination_type = r.termination;
-      su.ok = r.ok;
-      su.initial_cost = r.initial_cost;
-      su.final_cost = r.final_cost;
-      su.fixed_cost = 0.0;
-      su.trust_region_radius = r.radius;
-      su.num_lm_iterations = r.lm_iters;
-      su.sync_timeouts = 0;   // nothing to time out on: no hand-off between workgroups
-    }
+    TimeEnd();
+    for (int i = 0; i < n; ++i)
+      if (plan_.points[i].run) Summarize(i);   // (the PointOut of a point that did not run was not written)
     // write-back only after every point's result has been checked: a failed call changes nothing
     for (int i = 0; i < n; ++i) {
       if (!plan_.points[i].run || !sums_[i].ok) continue;

@@ -426,7 +426,28 @@ int sg_slam_solve_points(sg_slam* s, sg_map* map, const int32_t* points, int32_t
   SG_CAPI_END
 }
 
-// Diagnostics (not in the public header): HIP-event time of the k_point_lm launch (tools/points_bench.py).
+int sg_slam_triangulate_points(sg_slam* s, sg_map* map, const int32_t* points, int32_t n,
+                               const sg_triangulate_options* options, int32_t* solved,
+                               sg_triangulate_result* results, sg_solver_summary* summaries) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s && map && options, SG_EINVAL, "null argument");
+  SG_REQUIRE(n >= 0, SG_EINVAL, "negative point count");
+  if (n == 0) return SG_OK;   // nothing to triangulate: neither the handle nor the device is touched
+  SG_REQUIRE(points && solved, SG_EINVAL, "null point list or result array");
+  sg::PointSolver& ps = PointSolverOf(s);
+  ps.Triangulate(map, points, n, *options, s->options, solved, results, summaries);
+  // Slam::Run's bookkeeping (slam.cpp:517-518) over the points the polish ran on, in list order
+  for (const sg_solver_summary& sum : ps.summaries()) {
+    if (sum.termination_type == SG_DID_NOT_RUN) continue;
+    s->iterations += sum.num_iterations;
+    s->error = sum.final_cost;
+    s->last = sum;
+  }
+  SG_CAPI_END
+}
+
+// Diagnostics (not in the public header): HIP-event time of the k_point_lm launch (tools/points_bench.py); after
+// sg_slam_triangulate_points, of its one or two launches (tools/triangulate_bench.py).
 int sg_slam_debug_points_timing(sg_slam* s, int32_t enable) {
   SG_CAPI_BEGIN
   SG_REQUIRE(s, SG_EINVAL, "null handle");

@@ -19,6 +19,10 @@
 namespace sg {
 
 constexpr int kPointMinObs = 2;
+// sg_slam_triangulate_points (triangulate_math.h): the least gap between the two smallest eigenvalues of the 4x4
+// DLT matrix, relative to the largest, at which the null direction counts as determined.  Rounding leaves about
+// 1e-16 of the largest eigenvalue in every other one, so below 1e-12 the eigenvector is noise to 1e-4 or worse.
+constexpr double kTriMinRelGap = 1e-12;
 
 // One enabled observation of a listed point: the observed pixel and the map index of the observing frame.
 struct PointObs {

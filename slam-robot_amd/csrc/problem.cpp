@@ -266,6 +266,13 @@ void sg_solver_options_default(sg_solver_options* o) {
   o->always_linearize = 0;
 }
 
+void sg_triangulate_options_default(sg_triangulate_options* o) {
+  o->min_parallax = 0.0;   // gates off
+  o->max_error_px = 0.0;
+  o->refine = 0;
+  o->range = 2.0;          // main.cpp's CauchyLoss range
+}
+
 void sg_device_options_default(sg_device_options* o) {
   o->device = 0;
   o->precision = 0;

@@ -51,6 +51,32 @@ SG_HD bool Project(const T* q, const T* t, const T* k, const T* X, T* uv) {
   return true;
 }
 
+// The inverse of Project's image-side half (Camera::PlaneToPixel, localmap.h:38-56): pixel -> undistorted plane
+// coordinates (a, b) = (p.x / p.z, p.y / p.z).  The distortion is radial, so only the radius is solved for:
+// r (1 + k1 r^2 + k2 r^4 + k3 r^6) = r_d by Newton from r = r_d, 8 steps (converged to rounding for the lenses in
+// use; the reference's Camera::PixelToPlane, localmap.h:58-80, stops after three fixed-point rounds, which leave
+// about 0.1 px at k1 = -0.1 in the image corner).  r_d == 0 gives (0, 0).
+template <typename T>
+SG_HD void UndistortPixel(const T* k, const T* pt, T* ab) {
+  const T xd = (pt[0] - k[5]) / k[3], yd = (pt[1] - k[6]) / k[4];
+  const T rd = sqrt(xd * xd + yd * yd);
+  if (rd == T(0)) {   // (a NaN pixel falls through and stays NaN)
+    ab[0] = T(0);
+    ab[1] = T(0);
+    return;
+  }
+  T r = rd;
+  for (int it = 0; it < 8; ++it) {
+    const T r2 = r * r;
+    const T f = r * (T(1) + r2 * (k[0] + r2 * (k[1] + r2 * k[2]))) - rd;
+    const T df = T(1) + r2 * (T(3) * k[0] + r2 * (T(5) * k[1] + r2 * (T(7) * k[2])));
+    r = r - f / df;
+  }
+  const T s = r / rd;
+  ab[0] = xd * s;
+  ab[1] = yd * s;
+}
+
 // Value + analytic Jacobian of the projection.  Outputs (row-major, 2 rows):
 //   Jq[2][4]  d(uv)/d(q memory [x,y,z,w])     (global, before the local parameterization; if Jq != nullptr)
 //   Jt[2][3]  d(uv)/d(t)

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from .capi import (ProblemArrays, SgBaInfo, SgDeviceOptions, SgProblem, SgSolverOptions, SgSolverSummary,
-                   check, default_solver_options, load_library)
+                   SgTriangulateOptions, SgTriangulateResult, check, default_solver_options, load_library)
 from .scene import MapArrays
 
 
@@ -291,8 +291,36 @@ class Slam:
         return [bool(v) for v in solved]
 
     def point_summaries(self) -> list:
-        """Summary dicts of the last SolvePoints call, one per listed point."""
+        """Summary dicts of the last SolvePoints or TriangulatePoints call, one per listed point."""
         return list(getattr(self, "_point_summaries", []))
+
+    def TriangulatePoints(self, m: MapArrays, points, min_parallax: float = 0.0, max_error_px: float = 0.0,
+                          refine: bool = False, range_: float = 2.0) -> list:
+        """Linear multi-view triangulation (sg_slam_triangulate_points): each listed point's location from its
+        enabled observations alone, against the map's frames as they are, all points in one device launch.  The
+        location at entry is not read; point flags are not consulted.  min_parallax (rad) and max_error_px gate
+        the result, 0 = off; refine polishes the accepted points with SolvePoints' solver (CauchyLoss(range_)) on
+        the device.  Updates m.X of the accepted points in place and returns one bool per listed point;
+        triangulation_results() has their statuses and quality figures, point_summaries() the polish's."""
+        pts = np.ascontiguousarray(points, dtype=np.int32).reshape(-1)
+        n = len(pts)
+        solved = np.zeros(n, dtype=np.int32)
+        res = (SgTriangulateResult * max(n, 1))()
+        sums = (SgSolverSummary * max(n, 1))()
+        opt = SgTriangulateOptions(min_parallax=min_parallax, max_error_px=max_error_px, refine=int(bool(refine)),
+                                   range=range_)
+        ms = m.struct()
+        check(self.lib.sg_slam_triangulate_points(self.h, C.byref(ms), pts.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                                                  C.byref(opt), solved.ctypes.data_as(C.POINTER(C.c_int32)), res,
+                                                  sums), "Slam::TriangulatePoints")
+        self._triangulation_results = [res[i].as_dict() for i in range(n)]
+        self._point_summaries = [sums[i].as_dict() for i in range(n)]
+        return [bool(v) for v in solved]
+
+    def triangulation_results(self) -> list:
+        """Result dicts of the last TriangulatePoints call, one per listed point: status (a TRI_STATUS name),
+        num_obs, parallax (rad), max_error_px, rel_gap and the triangulated X (before the polish)."""
+        return list(getattr(self, "_triangulation_results", []))
 
     def ReprojectMap(self, m: MapArrays) -> float:
         mean = C.c_double()

@@ -78,6 +78,24 @@ class SgSolverSummary(C.Structure):
         return d
 
 
+TRI_STATUS = {0: "OK", 1: "DID_NOT_RUN", 2: "NO_BASELINE", 3: "DEGENERATE", 4: "BEHIND", 5: "LOW_PARALLAX",
+              6: "HIGH_ERROR"}
+
+
+class SgTriangulateOptions(C.Structure):
+    _fields_ = [("min_parallax", C.c_double), ("max_error_px", C.c_double), ("refine", C.c_int32),
+                ("range", C.c_double)]
+
+
+class SgTriangulateResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("num_obs", C.c_int32), ("parallax", C.c_double),
+                ("max_error_px", C.c_double), ("rel_gap", C.c_double), ("X", C.c_double * 4)]
+
+    def as_dict(self):
+        return {"status": TRI_STATUS.get(self.status, "?"), "num_obs": self.num_obs, "parallax": self.parallax,
+                "max_error_px": self.max_error_px, "rel_gap": self.rel_gap, "X": np.array(self.X[:])}
+
+
 class SgBaInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("num_frames", "num_points", "num_obs", "num_blocks", "n", "band_tiles",
                                          "cholesky_path", "num_pairs", "rank", "nranks", "cholesky_split",
@@ -320,6 +338,10 @@ SYMBOLS = {
                                             C.POINTER(SgSolverSummary)]),
     "sg_slam_solve_points": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32, C.c_double, _ip,
                                        C.POINTER(SgSolverSummary)]),
+    "sg_triangulate_options_default": (None, [C.POINTER(SgTriangulateOptions)]),
+    "sg_slam_triangulate_points": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32,
+                                             C.POINTER(SgTriangulateOptions), _ip, C.POINTER(SgTriangulateResult),
+                                             C.POINTER(SgSolverSummary)]),
     "sg_frontend_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SgTrackerOptions), C.POINTER(SgDeviceOptions)]),
     "sg_frontend_destroy": (None, [C.c_void_p]),
     "sg_frontend_track": (C.c_int, [C.c_void_p, _u8p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
