@@ -395,6 +395,90 @@ int sg_slam_triangulate_points(sg_slam* s, sg_map* map, const int32_t* points, i
                                sg_triangulate_result* results /*[n], may be NULL*/,
                                sg_solver_summary* summaries /*[n], may be NULL*/);
 
+/* Localization from scratch: given the points as they are, where is this frame, from its observations alone?
+ * sg_slam_solve_frame_poses needs a start inside the basin (the reference starts a new frame at the pose of two
+ * frames ago, main.cpp:540-552) and its Cauchy loss copes with a few bad correspondences, not with half of them;
+ * after a tracking loss, a fast turn or a revisit ("Consider loop closing when adding new points", main.cpp:10)
+ * nothing else here recovers.  This call does: P3P RANSAC on the device, then optionally that solver as the polish.
+ * The pose at entry is not read.  Per listed frame f, over the records of sg_slam_solve_frame_poses (observations
+ * with obs_disabled == 0 whose point is slam-usable, in map order; N of them), with no FrameDistance term:
+ *   1. Run rule: N < 4: SG_LOC_DID_NOT_RUN (decided before anything is launched).
+ *   2. Hypotheses: H = max_hypotheses rounded up to a multiple of 256 (anything above 2^20 is taken as 2^20).
+ *      Hypothesis h in [0, H) draws three distinct record indices from a counter-based hash of (seed, f, h), f being
+ *      the map's frame index (not the position in the list), with no state carried between hypotheses.  On 32-bit
+ *      unsigned arithmetic:
+ *          mix(x):  x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *          base = mix(mix(mix(seed) + f) + h);   r_j = mix(base ^ (0x9e3779b9 * (j + 1))),  j = 0, 1, 2
+ *          i0 = (r_0 * N) >> 32,  i1 = (r_1 * (N - 1)) >> 32,  i2 = (r_2 * (N - 2)) >> 32   (64-bit products)
+ *          if i1 >= i0: i1 += 1;   lo = min(i0, i1), hi = max(i0, i1);   if i2 >= lo: i2 += 1;  if i2 >= hi: i2 += 1
+ *      (csrc/pnp_math.h, PnpSample).  A sample containing a point with |X.w| < 1e-9 (X has unit 4-norm: a point
+ *      farther than 1e9 map units) yields no model; so does one with two equal bearings or three collinear points
+ *      (squared sine below 1e-20), and one whose P3P has no finite real solution.
+ *   3. Minimal solver, in fp64: the three pixels are undistorted to unit bearings (Newton on the radius, as in
+ *      sg_slam_triangulate_points), the points are X.xyz / X.w.  Grunert's P3P: a quartic in the ratio of two depths,
+ *      solved in closed form (Ferrari), up to four real roots in a fixed order (the position is the "root index");
+ *      each root's depths take three Newton steps on the three distance equations; the rotation comes from the
+ *      orthonormal triads of the two congruent triangles.  Poses are in the map's convention: p = q (X - t), Eigen
+ *      [x,y,z,w] memory, t the camera centre, unit q with q.w >= 0.
+ *   4. Scoring: every pose against all N records with the projection of sg_ba_evaluate (project.h:11-54, its
+ *      behind-camera rule included).  MSAC cost = sum over the records of min(e^2, tau^2), e the pixel error,
+ *      tau = threshold_px; a record the projection refuses counts tau^2.  It is formed as T tau^2 + s: T the
+ *      truncated records, s the sum of e^2 over the others in index order.  The winner has the smallest cost (as a
+ *      double).  Ties go to the pose with more inliers, then to the smaller s (on clean data with outliers present
+ *      every all-inlier sample's s vanishes in the rounding of T tau^2 + s; this keeps the most accurate of them,
+ *      not the first), then to the smaller h, then to the smaller root index.
+ *   5. Status: the first of sg_loc_status' rules that applies, in the order of the enum below.  An inlier is a
+ *      record with e^2 <= tau^2.
+ *   6. Polish (refine != 0, SG_LOC_OK frames): sg_slam_solve_frame_poses' solver on all N records with
+ *      CauchyLoss(range) and the handle's sg_solver_options, started at the winner, on the device without a host
+ *      round trip.  The written pose is the polish's when it ends with ok = 1 and its MSAC cost at tau is not larger
+ *      than the winner's (both from the same fixed-order reduction, ties as in step 4); otherwise the winner is
+ *      written and refined = 0.
+ *   7. solved[i] = 1 and q, t are written for exactly the SG_LOC_OK frames.  Nothing else of the map is written, and
+ *      a failing call writes nothing.
+ *   - A null s, map or options, n < 0, threshold_px <= 0 (or NaN), max_hypotheses <= 0, a frame index out of range
+ *     or listed twice: SG_EINVAL.  n == 0 returns SG_OK before the handle or the device is touched.
+ * results (may be NULL) receives each frame's sg_localize_result; obs_inlier (may be NULL, [map->num_obs]) 1 or 0
+ * for each record of an SG_LOC_OK frame, at the written pose, and -1 everywhere else; summaries (may be NULL) the
+ * polish's summary (SG_DID_NOT_RUN where it did not run).  sg_slam_iterations, sg_slam_error and
+ * sg_slam_last_summary move only by the polish, by the convention of sg_slam_solve_frame_poses.  No communicator is
+ * involved: rank-local on a sharded handle.
+ * Not in scope: adaptive early termination (the hypothesis count is fixed, which keeps results reproducible),
+ * degenerate-configuration tests beyond the ones of step 2, the FrameDistance term, any change to obs_disabled. */
+enum sg_loc_status {
+  SG_LOC_OK = 0,
+  SG_LOC_DID_NOT_RUN = 1,   /* fewer than 4 records (decided before anything is launched) */
+  SG_LOC_NO_MODEL = 2,      /* no hypothesis gave a finite pose */
+  SG_LOC_FEW_INLIERS = 3    /* the winner has fewer than max(min_inliers, 4) inliers */
+};
+
+typedef struct sg_localize_options {
+  double threshold_px;      /* tau: inlier threshold and MSAC truncation, px; > 0 */
+  int32_t max_hypotheses;   /* > 0; rounded up to a multiple of 256 */
+  int32_t min_inliers;      /* fewer inliers at the winner: SG_LOC_FEW_INLIERS (at least 4 are always required) */
+  uint32_t seed;
+  int32_t refine;           /* != 0: k_pose_lm from the winner */
+  double range;             /* CauchyLoss range of the polish (ignored when refine == 0) */
+} sg_localize_options;
+
+typedef struct sg_localize_result {
+  int32_t status, num_obs;           /* enum sg_loc_status; records N */
+  int32_t num_inliers, refined;      /* inliers at the written pose; 1: the written pose is the polish's */
+  int32_t best_hypothesis;           /* the winner's h; -1 without a model */
+  int32_t best_sample[3];            /* its record indices within the frame, in draw order; -1 without a model */
+  int32_t hypotheses, models;        /* H; hypotheses that produced at least one pose */
+  double msac_cost, inlier_rms_px;   /* at the written pose (the winner's when the frame is not SG_LOC_OK) */
+  double ransac_cost;                /* the winner's MSAC cost */
+  double q[4], t[3];                 /* the RANSAC winner, before the polish; zeros without a model */
+} sg_localize_result;
+
+void sg_localize_options_default(sg_localize_options* o);   /* 4.0, 1024, 8, seed 0, refine = 1, range = 2.0 */
+int sg_slam_localize_frames(sg_slam* s, sg_map* map, const int32_t* frames, int32_t n,
+                            const sg_localize_options* options, int32_t* solved /*[n]*/,
+                            sg_localize_result* results /*[n], may be NULL*/,
+                            int32_t* obs_inlier /*[map->num_obs], may be NULL*/,
+                            sg_solver_summary* summaries /*[n], may be NULL*/);
+
 /* ------------------------------------------------------------------------------------------------
  * Front end: HessianTracker (hessian.h:9-270) and the forward/backward matching step of Matcher
  * (matcher.cpp:173-206 TrackFeature, 247-251 the 3 -> 6 level retry).  A tracker holds `max_images`

@@ -21,6 +21,37 @@ struct PoseOut {
 };
 static_assert(sizeof(PoseOut) == 120, "written by k_pose_lm as 11 doubles and 8 ints");
 
+// Workgroup shape shared by k_pose_lm (ba_pose.hip) and k_pose_ransac / k_pose_select (ba_localize.hip).
+constexpr int kPoseThreads = 256;
+constexpr int kPoseWaves = kPoseThreads / 64;
+// Records of a frame held in LDS for the whole solve, element by element (six arrays, so a wave's lanes read
+// consecutive doubles): 48 KiB.  The records beyond are re-read from global memory in every sweep.
+constexpr int kPoseStage = 1024;
+
+// sg_slam_localize_frames rounds max_hypotheses up to a multiple of kPoseThreads; anything above this counts as this.
+constexpr int kLocalizeMaxHypotheses = 1 << 20;
+
+// What k_pose_ransac writes per workgroup (one slice of kPoseThreads hypotheses of one frame): the slice's best
+// pose in the order of loc_before (ba_localize.hip), or h = -1 when no hypothesis of the slice gave a pose.
+struct LocCandidate {
+  double cost, sumsq;   // sumsq: the inliers' e^2 summed in record order; cost: (N - inliers) tau^2 + sumsq
+  double q[4], t[3];
+  int32_t h, root;      // hypothesis, index of the quartic's root
+  int32_t inliers;      // records with e^2 <= tau^2
+  int32_t models;       // hypotheses of the slice that gave at least one pose
+};
+static_assert(sizeof(LocCandidate) == 88, "written by k_pose_ransac as 9 doubles and 4 ints");
+
+// What k_pose_select writes per listed frame: the figures at one pose (the RANSAC winner, or k_pose_lm's result).
+struct LocOut {
+  double cost, sumsq;   // MSAC cost (num_obs - inliers) tau^2 + sumsq; sum of e^2 over the inliers
+  double q[4], t[3];
+  int32_t status, num_obs, inliers;
+  int32_t h, root, sample[3];   // the winner's hypothesis, root index and record indices (-1 without a model)
+  int32_t models, pad;
+};
+static_assert(sizeof(LocOut) == 112, "written by k_pose_select as 9 doubles and 10 ints");
+
 class PoseSolver {
  public:
   // stream: the HIP stream to run on (the Slam facade passes its solver's); nullptr: a stream of its own
@@ -32,11 +63,24 @@ class PoseSolver {
   void Solve(sg_map* m, const int32_t* frames, int32_t n, double range, bool with_frame_distance,
              const sg_solver_options& o, int32_t* solved, sg_solver_summary* summaries);
   const std::vector<sg_solver_summary>& summaries() const { return sums_; }
-  // Development aid (tools/pose_bench.py): HIP-event time of the k_pose_lm launch of the calls that follow.
+  // sg_slam_localize_frames (ba_localize.hip): k_pose_ransac and k_pose_select on the listed frames and, with
+  // lo.refine, k_pose_lm from the winners and k_pose_select once more on its poses, all on the one stream (one
+  // upload, two to four launches, one download).  The entry poses are not read.  results, obs_inlier
+  // ([m->num_obs]) and summaries may be null; the polish's summaries are also kept in summaries().
+  void Localize(sg_map* m, const int32_t* frames, int32_t n, const sg_localize_options& lo,
+                const sg_solver_options& o, int32_t* solved, sg_localize_result* results, int32_t* obs_inlier,
+                sg_solver_summary* summaries);
+  // Development aid (tools/pose_bench.py, tools/localize_bench.py): HIP-event time of the k_pose_lm launch of the
+  // calls that follow; after Localize, of its two to four launches.
   void SetTiming(bool on) { timing_ = on; }
   double last_kernel_ms() const { return kernel_ms_; }
 
  private:
+  // The pieces Solve and Localize share.  LaunchLm: k_pose_lm on the n uploaded frames (frames_, off_, records_;
+  // out_ sized for n), on stream_.  Summarize: sums_[i] from out_h_[i] (SG_EDEVICE when the loop did not finish).
+  void LaunchLm(int32_t n, double range, const sg_solver_options& o);
+  void Summarize(int i);
+
   sg_device_options dev_;
   hipStream_t stream_ = nullptr;
   bool own_stream_ = false;
@@ -48,6 +92,13 @@ class PoseSolver {
   DBuf<PoseOut> out_;
   std::vector<PoseOut> out_h_;
   std::vector<sg_solver_summary> sums_;
+  // Localize's
+  DBuf<int32_t> frame_index_;
+  DBuf<LocCandidate> cand_;
+  DBuf<LocOut> loc_d_[2];        // at the RANSAC winner | at the polish's pose
+  DBuf<int32_t> flags_d_[2];     // per record, the same two
+  std::vector<LocOut> loc_h_[2];
+  std::vector<int32_t> flags_h_[2];
   bool timing_ = false;
   double kernel_ms_ = 0.0;
   hipEvent_t ev_[2] = {nullptr, nullptr};

@@ -24,11 +24,6 @@ namespace sg {
 
 namespace {
 
-constexpr int kPoseThreads = 256;
-constexpr int kPoseWaves = kPoseThreads / 64;
-// Records of a frame held in LDS for the whole solve, element by element (six arrays, so a wave's lanes read
-// consecutive doubles): 48 KiB.  The records beyond are re-read from global memory in every sweep.
-constexpr int kPoseStage = 1024;
 // A linearization's sums: the 21 upper entries of J^T J (u6 order) | J^T r (6) | cost | behind-camera count
 constexpr int kPoseNV = 29;
 constexpr int kVG = 21, kVCost = 27, kVFail = 28;
@@ -332,6 +327,63 @@ PoseSolver::~PoseSolver() {
   if (own_stream_ && stream_) (void)hipStreamDestroy(stream_);
 }
 
+void PoseSolver::LaunchLm(int32_t n, double range, const sg_solver_options& o) {
+  LmState s{};   // as BaSolver::Begin
+  s.max_iter = o.max_num_iterations;
+  s.max_invalid = o.max_num_consecutive_invalid_steps;
+  s.disable_term = o.disable_termination;
+  s.always_lin = o.always_linearize;
+  s.jacobi = o.jacobi_scaling;
+  s.ftol = o.function_tolerance;
+  s.gtol = o.gradient_tolerance;
+  s.ptol = o.parameter_tolerance;
+  s.min_rel_dec = o.min_relative_decrease;
+  s.max_radius = o.max_trust_region_radius;
+  s.min_radius = o.min_trust_region_radius;
+  s.min_diag = o.min_lm_diagonal;
+  s.max_diag = o.max_lm_diagonal;
+  s.need_lin = 1;
+  s.first = 1;
+  s.ok = 1;
+  s.termination = SG_NO_CONVERGENCE;
+  s.radius = o.initial_trust_region_radius;
+  s.decrease_factor = 2.0;
+  PoseArgs a{};
+  a.frames = frames_.ptr;
+  a.off = off_.ptr;
+  a.records = reinterpret_cast<const double*>(records_.ptr);
+  a.out = out_.ptr;
+  a.b = range * range;
+  a.inv_b = 1.0 / a.b;
+  a.fd_target = 150.0;   // FrameDistance(150.) with CauchyLoss(15) (slam.cpp:403-404)
+  a.fd_b2 = 15.0 * 15.0;
+  a.fd_inv_b2 = 1.0 / a.fd_b2;
+  // the bound of BaSolver::Solve's host loop: every iteration, rejected and invalid steps included
+  const long long cap =
+      (long long)std::max(o.max_num_iterations, 0) * (std::max(o.max_num_consecutive_invalid_steps, 0) + 2) + 16;
+  a.cap = (int32_t)std::min<long long>(cap, INT_MAX);
+  hipLaunchKernelGGL(k_pose_lm, dim3((unsigned)n), dim3(kPoseThreads), 0, stream_, a, s);
+  SG_HIP_CHECK(hipGetLastError());
+}
+
+void PoseSolver::Summarize(int i) {
+  const PoseOut& r = out_h_[i];
+  SG_REQUIRE(r.finished, SG_EDEVICE, "LM loop did not terminate on the device");
+  sg_solver_summary& su = sums_[i];
+  su.num_iterations = r.num_iterations;
+  su.num_successful_steps = r.n_succ;
+  su.num_unsuccessful_steps = r.n_unsucc;
+  su.num_invalid_steps = r.n_invalid;
+  su.termination_type = r.termination;
+  su.ok = r.ok;
+  su.initial_cost = r.initial_cost;
+  su.final_cost = r.final_cost;
+  su.fixed_cost = r.fixed_cost;
+  su.trust_region_radius = r.radius;
+  su.num_lm_iterations = r.lm_iters;
+  su.sync_timeouts = 0;   // nothing to time out on: no hand-off between workgroups
+}
+
 void PoseSolver::Solve(sg_map* m, const int32_t* frames, int32_t n, double range, bool with_frame_distance,
                        const sg_solver_options& o, int32_t* solved, sg_solver_summary* summaries) {
   SG_REQUIRE(m && (n == 0 || (frames && solved)), SG_EINVAL, "null argument");
@@ -349,47 +401,12 @@ void PoseSolver::Solve(sg_map* m, const int32_t* frames, int32_t n, double range
     io_.Up(records_, plan_.records);
     out_.Resize((size_t)n);
     io_.FlushUp(stream_);
-    LmState s{};   // as BaSolver::Begin
-    s.max_iter = o.max_num_iterations;
-    s.max_invalid = o.max_num_consecutive_invalid_steps;
-    s.disable_term = o.disable_termination;
-    s.always_lin = o.always_linearize;
-    s.jacobi = o.jacobi_scaling;
-    s.ftol = o.function_tolerance;
-    s.gtol = o.gradient_tolerance;
-    s.ptol = o.parameter_tolerance;
-    s.min_rel_dec = o.min_relative_decrease;
-    s.max_radius = o.max_trust_region_radius;
-    s.min_radius = o.min_trust_region_radius;
-    s.min_diag = o.min_lm_diagonal;
-    s.max_diag = o.max_lm_diagonal;
-    s.need_lin = 1;
-    s.first = 1;
-    s.ok = 1;
-    s.termination = SG_NO_CONVERGENCE;
-    s.radius = o.initial_trust_region_radius;
-    s.decrease_factor = 2.0;
-    PoseArgs a{};
-    a.frames = frames_.ptr;
-    a.off = off_.ptr;
-    a.records = reinterpret_cast<const double*>(records_.ptr);
-    a.out = out_.ptr;
-    a.b = range * range;
-    a.inv_b = 1.0 / a.b;
-    a.fd_target = 150.0;   // FrameDistance(150.) with CauchyLoss(15) (slam.cpp:403-404)
-    a.fd_b2 = 15.0 * 15.0;
-    a.fd_inv_b2 = 1.0 / a.fd_b2;
-    // the bound of BaSolver::Solve's host loop: every iteration, rejected and invalid steps included
-    const long long cap =
-        (long long)std::max(o.max_num_iterations, 0) * (std::max(o.max_num_consecutive_invalid_steps, 0) + 2) + 16;
-    a.cap = (int32_t)std::min<long long>(cap, INT_MAX);
     if (timing_) {
       for (hipEvent_t& e : ev_)
         if (!e) SG_HIP_CHECK(hipEventCreate(&e));
       SG_HIP_CHECK(hipEventRecord(ev_[0], stream_));
     }
-    hipLaunchKernelGGL(k_pose_lm, dim3((unsigned)n), dim3(kPoseThreads), 0, stream_, a, s);
-    SG_HIP_CHECK(hipGetLastError());
+    LaunchLm(n, range, o);
     if (timing_) SG_HIP_CHECK(hipEventRecord(ev_[1], stream_));
     out_h_.resize((size_t)n);
     io_.Down(out_h_.data(), out_.ptr, (size_t)n * sizeof(PoseOut));
@@ -401,21 +418,7 @@ void PoseSolver::Solve(sg_map* m, const int32_t* frames, int32_t n, double range
     }
     for (int i = 0; i < n; ++i) {
       if (!plan_.frames[i].run) continue;
-      const PoseOut& r = out_h_[i];
-      SG_REQUIRE(r.finished, SG_EDEVICE, "LM loop did not terminate on the device");
-      sg_solver_summary& su = sums_[i];
-      su.num_iterations = r.num_iterations;
-      su.num_successful_steps = r.n_succ;
-      su.num_unsuccessful_steps = r.n_unsucc;
-      su.num_invalid_steps = r.n_invalid;
-      su.termination_type = r.termination;
-      su.ok = r.ok;
-      su.initial_cost = r.initial_cost;
-      su.final_cost = r.final_cost;
-      su.fixed_cost = r.fixed_cost;
-      su.trust_region_radius = r.radius;
-      su.num_lm_iterations = r.lm_iters;
-      su.sync_timeouts = 0;   // nothing to time out on: no hand-off between workgroups
+      Summarize(i);
     }
     // write-back only after every frame's result has been checked: a failed call changes nothing
     for (int i = 0; i < n; ++i) {

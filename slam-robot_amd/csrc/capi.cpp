@@ -387,7 +387,30 @@ int sg_slam_solve_frame_poses(sg_slam* s, sg_map* map, const int32_t* frames, in
   SG_CAPI_END
 }
 
-// Diagnostics (not in the public header): HIP-event time of the k_pose_lm launch (tools/pose_bench.py).
+int sg_slam_localize_frames(sg_slam* s, sg_map* map, const int32_t* frames, int32_t n,
+                            const sg_localize_options* options, int32_t* solved, sg_localize_result* results,
+                            int32_t* obs_inlier, sg_solver_summary* summaries) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s && map && options, SG_EINVAL, "null argument");
+  SG_REQUIRE(n >= 0, SG_EINVAL, "negative frame count");
+  SG_REQUIRE(options->threshold_px > 0.0, SG_EINVAL, "threshold_px must be positive");
+  SG_REQUIRE(options->max_hypotheses > 0, SG_EINVAL, "max_hypotheses must be positive");
+  if (n == 0) return SG_OK;   // nothing to localize: neither the handle nor the device is touched
+  SG_REQUIRE(frames && solved, SG_EINVAL, "null frame list or result array");
+  sg::PoseSolver& ps = PoseSolverOf(s);
+  ps.Localize(map, frames, n, *options, s->options, solved, results, obs_inlier, summaries);
+  // Slam::Run's bookkeeping (slam.cpp:517-518) over the frames the polish ran on, in list order
+  for (const sg_solver_summary& sum : ps.summaries()) {
+    if (sum.termination_type == SG_DID_NOT_RUN) continue;
+    s->iterations += sum.num_iterations;
+    s->error = sum.final_cost;
+    s->last = sum;
+  }
+  SG_CAPI_END
+}
+
+// Diagnostics (not in the public header): HIP-event time of the k_pose_lm launch (tools/pose_bench.py); after
+// sg_slam_localize_frames, of its two to four launches (tools/localize_bench.py).
 int sg_slam_debug_pose_timing(sg_slam* s, int32_t enable) {
   SG_CAPI_BEGIN
   SG_REQUIRE(s, SG_EINVAL, "null handle");

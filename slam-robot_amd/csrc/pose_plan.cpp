@@ -13,7 +13,8 @@ constexpr int kPoseUnusableMask =
     (1 << SG_BAD_LOCATION) | (1 << SG_NO_BASELINE) | (1 << SG_NO_OBSERVATIONS) | (1 << SG_BAD_FEATURE);
 }  // namespace
 
-void PlanPoses(const sg_map& m, const int32_t* frames, int32_t n, bool with_frame_distance, PosePlan* out) {
+void PlanPoses(const sg_map& m, const int32_t* frames, int32_t n, bool with_frame_distance, PosePlan* out,
+               int min_obs, bool with_obs_index) {
   SG_REQUIRE(n >= 0, SG_EINVAL, "negative frame count");
   SG_REQUIRE(n == 0 || frames, SG_EINVAL, "null frame list");
   SG_REQUIRE(m.num_frames >= 0 && m.num_points >= 0 && m.num_obs >= 0 && m.num_cameras >= 0, SG_EINVAL,
@@ -21,6 +22,7 @@ void PlanPoses(const sg_map& m, const int32_t* frames, int32_t n, bool with_fram
   const int F = m.num_frames, P = m.num_points, M = m.num_obs;
   out->off.assign((size_t)n + 1, 0);
   out->records.clear();
+  out->obs.clear();
   out->frames.assign((size_t)n, PoseFrame{});
   out->num_run = 0;
   if (n == 0) return;
@@ -49,10 +51,12 @@ void PlanPoses(const sg_map& m, const int32_t* frames, int32_t n, bool with_fram
   for (int i = 0; i < n; ++i) off[i + 1] += off[i];
   // pass 2: the records, in map order within each frame
   out->records.resize((size_t)off[n]);
+  if (with_obs_index) out->obs.resize((size_t)off[n]);
   std::vector<int32_t> fill(off.begin(), off.end() - 1);
   for (int o = 0; o < M; ++o) {
     const int i = slot[m.obs_frame[o]];
     if (i < 0 || !usable(o)) continue;
+    if (with_obs_index) out->obs[(size_t)fill[i]] = o;
     PoseRecord& r = out->records[(size_t)fill[i]++];
     r.u = m.obs_pt[2 * (size_t)o];
     r.v = m.obs_pt[2 * (size_t)o + 1];
@@ -67,7 +71,7 @@ void PlanPoses(const sg_map& m, const int32_t* frames, int32_t n, bool with_fram
     const int prev = m.frame_prev[f];
     pf.has_dist = with_frame_distance && prev >= 0;
     if (prev >= 0) std::memcpy(pf.tprev, m.t + 3 * (size_t)prev, sizeof(pf.tprev));
-    pf.run = off[i + 1] - off[i] >= kPoseMinObs;
+    pf.run = off[i + 1] - off[i] >= min_obs;
     out->num_run += pf.run;
   }
 }

@@ -19,6 +19,9 @@
 namespace sg {
 
 constexpr int kPoseMinObs = 3;
+// sg_slam_localize_frames' run rule: a minimal P3P sample takes three records and leaves up to four poses; the
+// fourth record is the fewest that can tell them apart.
+constexpr int kLocalizeMinObs = 4;
 
 // One usable observation: the observed pixel and its point's homogeneous location.
 struct PoseRecord {
@@ -41,12 +44,14 @@ struct PosePlan {
   std::vector<int32_t> off;         // [n + 1] records of requested frame i: off[i] .. off[i + 1]
   std::vector<PoseRecord> records;  // [off[n]]
   std::vector<PoseFrame> frames;    // [n]
+  std::vector<int32_t> obs;         // [off[n]] each record's observation index in the map (with_obs_index only)
   int num_run = 0;                  // frames with run = 1
 };
 
 // Throws sg::Error(SG_EINVAL) on a frame index out of range or listed twice and on a map whose indices are out
-// of range.  n >= 0; frames may be null when n == 0.
-void PlanPoses(const sg_map& m, const int32_t* frames, int32_t n, bool with_frame_distance, PosePlan* out);
+// of range.  n >= 0; frames may be null when n == 0.  min_obs: the fewest records a frame needs for run = 1.
+void PlanPoses(const sg_map& m, const int32_t* frames, int32_t n, bool with_frame_distance, PosePlan* out,
+               int min_obs = kPoseMinObs, bool with_obs_index = false);
 
 }  // namespace sg
 

@@ -273,6 +273,15 @@ void sg_triangulate_options_default(sg_triangulate_options* o) {
   o->range = 2.0;          // main.cpp's CauchyLoss range
 }
 
+void sg_localize_options_default(sg_localize_options* o) {
+  o->threshold_px = 4.0;
+  o->max_hypotheses = 1024;
+  o->min_inliers = 8;
+  o->seed = 0;
+  o->refine = 1;
+  o->range = 2.0;          // main.cpp's CauchyLoss range
+}
+
 void sg_device_options_default(sg_device_options* o) {
   o->device = 0;
   o->precision = 0;

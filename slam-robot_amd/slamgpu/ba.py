@@ -10,8 +10,9 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import (ProblemArrays, SgBaInfo, SgDeviceOptions, SgProblem, SgSolverOptions, SgSolverSummary,
-                   SgTriangulateOptions, SgTriangulateResult, check, default_solver_options, load_library)
+from .capi import (ProblemArrays, SgBaInfo, SgDeviceOptions, SgLocalizeOptions, SgLocalizeResult, SgProblem,
+                   SgSolverOptions, SgSolverSummary, SgTriangulateOptions, SgTriangulateResult, check,
+                   default_solver_options, load_library)
 from .scene import MapArrays
 
 
@@ -272,8 +273,46 @@ class Slam:
         return [bool(v) for v in solved]
 
     def frame_pose_summaries(self) -> list:
-        """Summary dicts of the last SolveFramePoses call, one per listed frame."""
+        """Summary dicts of the last SolveFramePoses call, or of the polish of the last LocalizeFrames call, one per
+        listed frame."""
         return list(getattr(self, "_pose_summaries", []))
+
+    def LocalizeFrames(self, m: MapArrays, frames, threshold_px: float = 4.0, max_hypotheses: int = 1024,
+                       min_inliers: int = 8, seed: int = 0, refine: bool = True, range_: float = 2.0) -> list:
+        """Localization from scratch (sg_slam_localize_frames): each listed frame's pose from its usable
+        observations and the map's points as they are, by P3P RANSAC on the device (max_hypotheses three-point
+        samples per frame, MSAC at threshold_px) and, with refine, SolveFramePoses' solver (CauchyLoss(range_)) from
+        the winner.  The pose at entry is not read.  Updates m.q / m.t of the localized frames in place and returns
+        one bool per listed frame; localization_results() has their statuses and figures,
+        localization_inliers() the per-observation inlier flags, frame_pose_summaries() the polish's summaries."""
+        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        n = len(fr)
+        solved = np.zeros(n, dtype=np.int32)
+        res = (SgLocalizeResult * max(n, 1))()
+        sums = (SgSolverSummary * max(n, 1))()
+        inl = np.full(max(m.num_obs, 1), -1, dtype=np.int32)
+        opt = SgLocalizeOptions(threshold_px=threshold_px, max_hypotheses=max_hypotheses, min_inliers=min_inliers,
+                                seed=seed, refine=int(bool(refine)), range=range_)
+        ms = m.struct()
+        check(self.lib.sg_slam_localize_frames(self.h, C.byref(ms), fr.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                                               C.byref(opt), solved.ctypes.data_as(C.POINTER(C.c_int32)), res,
+                                               inl.ctypes.data_as(C.POINTER(C.c_int32)), sums),
+              "Slam::LocalizeFrames")
+        self._localization_results = [res[i].as_dict() for i in range(n)]
+        self._localization_inliers = inl[:m.num_obs]
+        self._pose_summaries = [sums[i].as_dict() for i in range(n)]
+        return [bool(v) for v in solved]
+
+    def localization_results(self) -> list:
+        """Result dicts of the last LocalizeFrames call, one per listed frame: status (a LOC_STATUS name), num_obs,
+        num_inliers, refined, best_hypothesis, best_sample, hypotheses, models, msac_cost, inlier_rms_px,
+        ransac_cost and the RANSAC winner's q, t (before the polish)."""
+        return list(getattr(self, "_localization_results", []))
+
+    def localization_inliers(self) -> np.ndarray:
+        """int32 per observation of the map after the last LocalizeFrames call: 1 / 0 for the records of the
+        localized frames at the written pose, -1 everywhere else."""
+        return np.array(getattr(self, "_localization_inliers", np.zeros(0, dtype=np.int32)))
 
     def SolvePoints(self, m: MapArrays, points, range_: float) -> list:
         """Structure-only bundle adjustment (sg_slam_solve_points): each listed point's location against the map's

@@ -96,6 +96,28 @@ class SgTriangulateResult(C.Structure):
                 "max_error_px": self.max_error_px, "rel_gap": self.rel_gap, "X": np.array(self.X[:])}
 
 
+LOC_STATUS = {0: "OK", 1: "DID_NOT_RUN", 2: "NO_MODEL", 3: "FEW_INLIERS"}
+
+
+class SgLocalizeOptions(C.Structure):
+    _fields_ = [("threshold_px", C.c_double), ("max_hypotheses", C.c_int32), ("min_inliers", C.c_int32),
+                ("seed", C.c_uint32), ("refine", C.c_int32), ("range", C.c_double)]
+
+
+class SgLocalizeResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("num_obs", C.c_int32), ("num_inliers", C.c_int32), ("refined", C.c_int32),
+                ("best_hypothesis", C.c_int32), ("best_sample", C.c_int32 * 3), ("hypotheses", C.c_int32),
+                ("models", C.c_int32), ("msac_cost", C.c_double), ("inlier_rms_px", C.c_double),
+                ("ransac_cost", C.c_double), ("q", C.c_double * 4), ("t", C.c_double * 3)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["status"] = LOC_STATUS.get(self.status, "?")
+        d["best_sample"] = tuple(self.best_sample[:])
+        d["q"], d["t"] = np.array(self.q[:]), np.array(self.t[:])
+        return d
+
+
 class SgBaInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("num_frames", "num_points", "num_obs", "num_blocks", "n", "band_tiles",
                                          "cholesky_path", "num_pairs", "rank", "nranks", "cholesky_split",
@@ -338,6 +360,9 @@ SYMBOLS = {
                                             C.POINTER(SgSolverSummary)]),
     "sg_slam_solve_points": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32, C.c_double, _ip,
                                        C.POINTER(SgSolverSummary)]),
+    "sg_localize_options_default": (None, [C.POINTER(SgLocalizeOptions)]),
+    "sg_slam_localize_frames": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32, C.POINTER(SgLocalizeOptions),
+                                          _ip, C.POINTER(SgLocalizeResult), _ip, C.POINTER(SgSolverSummary)]),
     "sg_triangulate_options_default": (None, [C.POINTER(SgTriangulateOptions)]),
     "sg_slam_triangulate_points": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32,
                                              C.POINTER(SgTriangulateOptions), _ip, C.POINTER(SgTriangulateResult),
