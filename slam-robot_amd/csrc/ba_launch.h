@@ -16,6 +16,7 @@
 //                 PlanPointOrder, PlanObservations), the work lists (PlanSweep, PlanSchur, PlanReduceLists,
 //                 PlanFrameDistance, PlanIntrLists, PlanLoBlk), PlanEnvelope (Cholesky envelope, k_S_reduce tile
 //                 lists) and PlanChol (the Cholesky kernel choice)
+//   ba_chain.cpp  the planner of one LM iteration (ba_chain.h): which of the launchers below run, in which order and mode
 #ifndef SG_BA_LAUNCH_H_
 #define SG_BA_LAUNCH_H_
 

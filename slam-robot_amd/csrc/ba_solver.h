@@ -4,12 +4,12 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <chrono>
 #include <memory>
 #include <string>
 #include <vector>
 
+#include "ba_chain.h"
 #include "ba_kernels.h"
 #include "ba_plan.h"
 #include "common.h"
@@ -86,33 +86,13 @@ class BaSolver {
   size_t border_lds_max_ = 0;  // k_chol_border's dynamic LDS limit
   DBuf<double> Wg_;            // k_chol_tiles' back-substitution tiles W_KJ = U_KK^-1 U_KJ (+ the bottom half's)
   DBuf<int32_t> tflag_;        // dissected band hand-off counters {bottom done, top done}
-  // tests only: force the dissected Cholesky's separator wait to time out (k_chol_tiles flags bit 2)
-  bool chol_force_tmo_ = getenv("SG_CHOL_FORCE_TIMEOUT") && atoi(getenv("SG_CHOL_FORCE_TIMEOUT")) != 0;
-  // SG_CHOL_ZPRE=0: k_chol_tiles factors D_0 itself instead of starting from k_S_reduce's Z_0 (A/B, tests)
-  bool chol_zpre_off_ = getenv("SG_CHOL_ZPRE") && atoi(getenv("SG_CHOL_ZPRE")) == 0;
-  // SG_CHOL_STILE=0: k_chol_tiles loads its tiles from row-major S instead of k_S_reduce's tile-major copy (A/B, tests)
-  bool chol_stile_off_ = getenv("SG_CHOL_STILE") && atoi(getenv("SG_CHOL_STILE")) == 0;
-  bool chol_stile_last_ = false;   // the last LM iteration enqueued took that copy (sg_ba_info.cholesky_stile)
-  // SG_CHOL_DELAY=bottom|top (tests only): that workgroup of the dissected Cholesky sleeps a few tens of µs, the
-  // bottom before its first phase, the top just before its poll, so both arrival orders of the hand-off run
-  int chol_delay_ = !getenv("SG_CHOL_DELAY") ? 0
-                    : std::string(getenv("SG_CHOL_DELAY")) == "bottom" ? 64
-                    : std::string(getenv("SG_CHOL_DELAY")) == "top"    ? 128
-                                                                       : 0;
-  bool pack_force_ = getenv("SG_PACK_S") != nullptr;   // pack/unpack S on one rank too (tests the path)
-  // speculative linearization (k_update_lin: the candidate pass linearizes at the candidate; k_linearize runs
-  // only in a solve's first iteration); SG_SPEC=0: k_point_update + k_linearize every iteration
-  bool spec_ = !(getenv("SG_SPEC") && atoi(getenv("SG_SPEC")) == 0);
+  RunKnobs knobs_;   // the switches read at construction (ba_chain.h)
+  bool chol_stile_last_ = false;   // the last LM iteration enqueued loaded k_S_reduce's tile-major copy of S
+                                   // (sg_ba_info.cholesky_stile)
   size_t jslot_ = 0, cslot_ = 0;   // doubles per slot of J and cam_slab
-  // merged exchange of landmark shards (ba_solver.hip, EnqueueIterations): 1 default (shards), 0 off (SG_XCHG_MERGE=0),
-  // 2 forced on one rank too (SG_XCHG_MERGE=force, tests)
-  int merge_ = getenv("SG_XCHG_MERGE") ? (std::string(getenv("SG_XCHG_MERGE")) == "force" ? 2 : atoi(getenv("SG_XCHG_MERGE")) != 0)
-                                       : 1;
   size_t ntail_ = 0;   // doubles of the merged exchange's tail
   bool pending_decision_ = false;   // speculative chain: the last enqueued step awaits its decision
   int32_t nallreduce_ = 0;   // landmark-shard all-reduces issued (sg_ba_info.num_allreduces)
-  // tests: issue the communicator's collectives on one rank too (SG_COMM_FORCE=1: RCCL with one rank is a copy)
-  bool comm_force_ = getenv("SG_COMM_FORCE") && atoi(getenv("SG_COMM_FORCE")) == 1;
   bool stamp_on_ = false;
   int wt_stores_ = 0;                   // Dev::wt of the last full load (SG_WT_STORES)
   int ncu_ = 256;                       // compute units (Schur segment count), queried once

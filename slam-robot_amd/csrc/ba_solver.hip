@@ -14,7 +14,8 @@
 //   k_chol_tiles   dissected tiled band Cholesky of S, back substitution, candidate poses
 //   k_update_lin   point back substitution, model and candidate cost, and the linearization at the candidate
 //   k_cam_reduce   the candidate's camera partials and update scalars reduced, and the LM decision (mode 2)
-// Landmark shards add the exchanges of DESIGN.md 5 (pack, all-reduce, unpack) and the separate decision.
+// Landmark shards add the exchanges of DESIGN.md 5 (pack, all-reduce, unpack) and the separate decision; the chain
+// of every regime is planned in ba_chain.cpp.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -63,7 +64,9 @@ void BaSolver::LaunchCholTiles(bool stamp, dim3 grid, const Dev& d, int flags) {
   }
 }
 
-BaSolver::BaSolver(const sg_device_options& dev) : dev_(dev) {
+static RunKnobs ReadRunKnobs();   // (beside ReadLoadKnobs, below)
+
+BaSolver::BaSolver(const sg_device_options& dev) : dev_(dev), knobs_(ReadRunKnobs()) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(SG_ENODEV, "no HIP device available");
   SG_REQUIRE(dev.device >= 0 && dev.device < ndev, SG_ENODEV, "device ordinal out of range");
@@ -121,7 +124,7 @@ void BaSolver::CommInitHost(int nranks, int rank, int (*fn)(double*, long long, 
 int BaSolver::nranks() const { return comm_ ? comm_->nranks() : 1; }
 
 void BaSolver::AllReduceSum(double* buf, size_t n) {
-  if (comm_ && (comm_->nranks() > 1 || comm_force_)) {
+  if (comm_ && (comm_->nranks() > 1 || knobs_.comm_force)) {
     comm_->AllReduceSum(buf, n, stream_);
     ++nallreduce_;
   }
@@ -146,6 +149,23 @@ static LoadKnobs ReadLoadKnobs() {
   k.chol_sep7 = is("SG_CHOL_SEP", kTB - 1);
   k.stamp = getenv("SG_STAMP") && getenv("SG_STAMP")[0] == '1';
   if (const char* e = getenv("SG_WT_STORES")) k.wt_stores = atoi(e) & (kWtJ | kWtCam | kWtSchur);
+  return k;
+}
+
+// The knobs of the iteration chain (ba_chain.h), read once when the solver is created: a caller sets the switches,
+// then creates its handle.
+static RunKnobs ReadRunKnobs() {
+  auto is = [](const char* name, int v) { return getenv(name) && atoi(getenv(name)) == v; };
+  auto str = [](const char* name) { return std::string(getenv(name) ? getenv(name) : ""); };
+  RunKnobs k;
+  k.spec = !is("SG_SPEC", 0);
+  if (getenv("SG_XCHG_MERGE")) k.merge = str("SG_XCHG_MERGE") == "force" ? 2 : !is("SG_XCHG_MERGE", 0);
+  k.pack_force = getenv("SG_PACK_S") != nullptr;
+  k.comm_force = is("SG_COMM_FORCE", 1);
+  k.chol_zpre = !is("SG_CHOL_ZPRE", 0);
+  k.chol_stile = !is("SG_CHOL_STILE", 0);
+  k.chol_force_tmo = getenv("SG_CHOL_FORCE_TIMEOUT") && !is("SG_CHOL_FORCE_TIMEOUT", 0);
+  k.chol_delay = str("SG_CHOL_DELAY") == "bottom" ? 64 : str("SG_CHOL_DELAY") == "top" ? 128 : 0;
   return k;
 }
 
@@ -225,7 +245,7 @@ void BaSolver::Load(const sg_problem& p) {
     }
     // incremental update: every rank must take the same path (the full path has a load-time all-reduce)
     double changed = vcode != SG_OK ? 2.0 : (loaded_ && SameStructure(p)) ? 0.0 : 1.0;
-    if (comm_ && (comm_->nranks() > 1 || comm_force_)) {
+    if (comm_ && (comm_->nranks() > 1 || knobs_.comm_force)) {
       DBuf<double> flag;
       flag.Upload(std::vector<double>{changed}, stream_);
       comm_->AllReduceMax(flag.ptr, 1, stream_);
@@ -324,7 +344,7 @@ void BaSolver::Load(const sg_problem& p) {
   // Landmark shards: S is summed over every rank's points, so each rank must factor it with the envelope of
   // the whole problem (the union of the shards' envelopes), not of its own points.  One max all-reduce of
   // -lo(J) at load time.
-  if (comm_ && (comm_->nranks() > 1 || comm_force_) && NB_ > 0) {
+  if (comm_ && (comm_->nranks() > 1 || knobs_.comm_force) && NB_ > 0) {
     std::vector<double> neg(NB_);
     for (int b = 0; b < NB_; ++b) neg[b] = -(double)wl.lo_blk[b];
     DBuf<double> env;
@@ -676,7 +696,7 @@ Dev BaSolver::MakeDev() {
       d.lin_scal[sl] = lin_scal_.ptr + sl * (size_t)std::max(wk_.nlin, 1) * kNScal;
     }
   }
-  d.spec = spec_ ? 1 : 0;
+  d.spec = knobs_.spec ? 1 : 0;
   d.scale_p = scale_p_.ptr;
   d.diag_p = diag_p_.ptr;
   d.Vinv = Vinv_.ptr;
@@ -856,7 +876,7 @@ void BaSolver::Begin(const sg_solver_options& o) {
   s.radius = o.initial_trust_region_radius;
   s.decrease_factor = 2.0;
   hipLaunchKernelGGL(k_set_state, dim3(1), dim3(64), 0, stream_, s, st_.ptr);
-  if (began_again && spec_) {
+  if (began_again && knobs_.spec) {
     // k_cam_reduce keeps the wide-chunk camera accumulators in speculative mode: clear both slots for the
     // restart's first k_linearize (a fresh Load has zeroed them)
     ZeroList z{};
@@ -894,151 +914,89 @@ void BaSolver::Iterate(int n) {
   EnqueueIterations(n);
 }
 
+// The timer an op's launches are counted under (-1: none), in ChainOp's order.
+static const int kChainTimer[(int)ChainOp::kCount] = {
+    kKLin,        // Linearize
+    kKCamReduce,  // CamReduce (the closing one, with two extra workgroups, counts as the update reduce: below)
+    kKDecide,     // Decide
+    -1,           // AllReduceCam
+    -1,           // IntrLinearize
+    kKCamFinal,   // CamFinalize
+    kKSchur,      // Schur
+    kKSReduce,    // SReduce
+    -1,           // IntrSchur
+    kKXchg,       // Exchange: pack, all-reduce, unpack
+    kKChol,       // Chol
+    -1,           // IntrStep
+    kKPointUpd,   // UpdateLin
+    kKPointUpd,   // PointUpdate
+    kKUpdRed,     // UpdReduce
+    -1,           // AllReduceUpd
+};
+
+// Enqueue n LM iterations: the launches ba_chain.cpp plans for each (which, in which order and mode: see there), with
+// the grids, buffers and the Cholesky kernel the load chose.
 void BaSolver::EnqueueIterations(int n) {
-  Dev d = MakeDev();
+  const Dev d = MakeDev();
+  const ChainShape shape{comm_ && comm_->nranks() > 1, d.assemble != 0, nk_, chol_.tiles, chol_.border};
+  const int nv = NB_ * kCamV;
+  const int npanel = (n_ + kCholNb - 1) / kCholNb;
+  const dim3 pg(npanel + 1, 4);   // k_S_pack / k_S_unpack_fin
+  const int32_t* panel_jend = (const int32_t*)work_i_.ptr;
+  const int32_t* pack_off = (const int32_t*)pack_off_.ptr;
+  auto run = [&](const ChainStep& step) {
+    for (int i = 0; i < step.n; ++i) {
+      const ChainCall c = step.ops[i];
+      const int timer = c.op == ChainOp::CamReduce && c.a == 2 ? (int)kKUpdRed : kChainTimer[(int)c.op];
+      if (timer >= 0) TimedLaunchBegin(timer);
+      switch (c.op) {
+        case ChainOp::Linearize: LaunchLinearize(d); break;
+        case ChainOp::CamReduce: LaunchCamReduceK(NB_ + c.a, stream_, d, c.b); break;
+        case ChainOp::Decide: LaunchDecideK(stream_, d, c.a); break;
+        case ChainOp::AllReduceCam: AllReduceSum(xchg_cam_.ptr, (size_t)nv + kXNum + nranks()); break;
+        case ChainOp::IntrLinearize: LaunchIntrLinearizeK(stream_, d, n_, nk_, NB_, ncam_, M_, wk_.intr_nsl); break;
+        case ChainOp::CamFinalize: LaunchCamFinalizeK(stream_, d, c.a, 0); break;
+        case ChainOp::Schur: LaunchSchurK(std::max(wk_.nseg, 1), wk_.nwide, c.a, stream_, d); break;
+        case ChainOp::SReduce: LaunchSReduceK(std::max(env_.nstile + NB_, 1), stream_, d, c.a, c.b); break;
+        case ChainOp::IntrSchur: LaunchIntrSchurK(stream_, d, n_, nk_, NB_, ncam_, P_, wk_.intr_nsl); break;
+        case ChainOp::Exchange:
+          LaunchSPackK(pg, stream_, S_.ptr, n_, panel_jend, pack_off, npanel, Spk_.ptr, 0);
+          AllReduceSum(Spk_.ptr, env_.npack + (c.a ? ntail_ : 0));
+          if (c.b)
+            LaunchSUnpackFinK(pg, stream_, d, panel_jend, pack_off, npanel, Spk_.ptr);
+          else
+            LaunchSPackK(pg, stream_, S_.ptr, n_, panel_jend, pack_off, npanel, Spk_.ptr, 1);
+          break;
+        case ChainOp::Chol:
+          if (chol_.tiles)
+            LaunchCholTiles(d.stamps != nullptr, dim3(chol_.nd > 0 ? 2 : 1), d,
+                            (chol_.cand_lds ? 2 : 0) | (knobs_.chol_force_tmo ? 4 : 0) | (c.a ? 16 : 0) | (c.b ? 32 : 0) |
+                                knobs_.chol_delay);
+          else if (chol_.window)
+            LaunchCholWindowK(d.stamps != nullptr, stream_, d, panel_jend, rdg_.ptr);
+          else
+            LaunchCholGlobalK(chol_.gstage, (size_t)std::max(n_, 1) * 8 * (chol_.gstage ? 1 + kCholNb : 1), stream_, d,
+                              panel_jend, rdg_.ptr);
+          break;
+        case ChainOp::IntrStep: LaunchIntrStepK(stream_, d); break;
+        case ChainOp::UpdateLin: LaunchUpdateLin(d); break;
+        case ChainOp::PointUpdate: LaunchPointUpdateK(std::max(wk_.npu, 1), stream_, d); break;
+        case ChainOp::UpdReduce: LaunchUpdReduceK(stream_, d, c.a); break;
+        case ChainOp::AllReduceUpd: AllReduceSum(xchg_upd_.ptr, kUNum); break;
+        case ChainOp::kCount: break;
+      }
+      if (timer >= 0) TimedLaunchEnd(timer);
+    }
+  };
   for (int it = 0; it < n; ++it) {
-    // speculative mode: only a solve's first iteration linearizes here; later ones find the linearization of
-    // the accepted point in the slot k_update_lin filled (k_linearize would exit at once: no launch)
-    if (!spec_ || need_seq_) {
-      TimedLaunchBegin(kKLin);
-      LaunchLinearize(d);
-      TimedLaunchEnd(kKLin);
-    }
-    const bool first_it = need_seq_;
+    const ChainStep step = PlanIteration(shape, knobs_, need_seq_, pending_decision_);
+    run(step);
     need_seq_ = false;
-    // Landmark shards exchange twice per LM iteration after a solve's first: k_S_reduce assembles each rank's
-    // own camera blocks (and, on rank 0, the FrameDistance terms) into its partial S, and the camera gradient,
-    // diagonal and cost scalars ride in the same all-reduce as the band of S (k_cam_finalize modes 1 and 2);
-    // the first iteration sums the camera blocks first (the Jacobi scale of the camera columns comes from
-    // them), then S.  SG_XCHG_MERGE=0: the three-exchange chain every iteration; =force: the merged chain on
-    // one rank too (tests the path).
-    const bool multi_x = (comm_ && comm_->nranks() > 1);
-    const bool merged = !first_it && nk_ == 0 && (merge_ == 2 || (multi_x && merge_ == 1));
-    const int nv = NB_ * kCamV;
-    // Speculative chain: the previous iteration ended with the candidate's camera reduce and the update scalars
-    // (k_cam_reduce mode 1, + their all-reduce on shards); the pending decision is taken by k_cam_finalize
-    // itself (one rank, or merged shards), else by k_decide, which then also makes the accepted candidate's
-    // blocks current.  No pending decision (a batch's first iteration: EnqueueIterations settles it at the
-    // end of every batch): the current blocks are in place.
-    // One rank (no free intrinsics): the previous iteration's reduce took the decision (k_cam_reduce mode 2) and
-    // this iteration's finalize pass runs inside the k_schur launch.
-    // Merged landmark shards (speculative chain): the pending decision as its own small launch (k_decide, which
-    // also makes an accepted candidate's blocks current), the finalize pass's mode 1 inside the k_schur launch,
-    // and its mode 2 inside the unpack after the band exchange (k_S_unpack_fin): two single-workgroup launches of
-    // the replicated chain less per iteration.
-    const bool fin_in_schur = spec_ && !first_it && !multi_x && nk_ == 0 && !merged;
-    const bool fin1_in_schur = spec_ && merged;
-    bool decide_in_fin = false;
-    if (fin_in_schur) {
-      // (nothing pending: the candidate blocks of an accepted step are taken by the pass)
-    } else if (spec_ && !first_it) {
-      if (pending_decision_) {
-        decide_in_fin = nk_ == 0 && !fin1_in_schur && (merged || !multi_x);
-        if (!decide_in_fin) {
-          TimedLaunchBegin(kKDecide);
-          LaunchDecideK(stream_, d, 1);
-          TimedLaunchEnd(kKDecide);
-        }
-        pending_decision_ = false;
-      }
-    } else {
-      TimedLaunchBegin(kKCamReduce);
-      LaunchCamReduceK(NB_ + 1, stream_, d, 0);
-      TimedLaunchEnd(kKCamReduce);
-    }
-    if (!merged) AllReduceSum(xchg_cam_.ptr, (size_t)nv + kXNum + nranks());
-    if (nk_) {
-      LaunchIntrLinearizeK(stream_, d, n_, nk_, NB_, ncam_, M_, wk_.intr_nsl);
-    }
-    if (!fin_in_schur && !fin1_in_schur) {
-      TimedLaunchBegin(kKCamFinal);
-      LaunchCamFinalizeK(stream_, d, merged ? 1 : 0, decide_in_fin ? 1 : 0);
-      TimedLaunchEnd(kKCamFinal);
-    }
-    TimedLaunchBegin(kKSchur);
-    LaunchSchurK(std::max(wk_.nseg, 1), wk_.nwide, fin_in_schur ? 1 : (fin1_in_schur ? 2 : 0), stream_, d);
-    TimedLaunchEnd(kKSchur);
-    TimedLaunchBegin(kKSReduce);
-    const int nwv = env_.nstile + NB_;
-    // S is final after k_S_reduce (one rank, no free intrinsics, no merged damping; a forced pack / unpack on one
-    // rank is a copy): it also factors the first diagonal tile for k_chol_tiles (flags bit 4)
-    const int samode = merged ? 2 : (d.assemble ? 1 : 0);
-    const bool zpre = chol_.tiles && !chol_.border && nk_ == 0 && samode == 1 && !(multi_x || merged) && !chol_zpre_off_;
-    // ... and writes the band a second time, tile-major in the order and layout k_chol_tiles consumes (St; flags bit 5)
-    const bool stile = chol_.tiles && !chol_.border && nk_ == 0 && samode == 1 && !(multi_x || merged) && !pack_force_ &&
-                       !chol_stile_off_;
-    chol_stile_last_ = stile;
-    LaunchSReduceK(std::max(nwv, 1), stream_, d, samode, (zpre ? 1 : 0) | (stile ? 2 : 0));
-    TimedLaunchEnd(kKSReduce);
-    if (nk_) {
-      LaunchIntrSchurK(stream_, d, n_, nk_, NB_, ncam_, P_, wk_.intr_nsl);
-    }
-    if (multi_x || pack_force_ || merged) {
-      // the band of S and the rhs partial are summed over landmark shards (packed: the band only), with the
-      // merged tail after them
-      const int npanel = (n_ + kCholNb - 1) / kCholNb;
-      const dim3 pg(npanel + 1, 4);
-      TimedLaunchBegin(kKXchg);   // pack, all-reduce, unpack
-      LaunchSPackK(pg, stream_, S_.ptr, n_, (const int32_t*)work_i_.ptr, (const int32_t*)pack_off_.ptr, npanel,
-                   Spk_.ptr, 0);
-      AllReduceSum(Spk_.ptr, env_.npack + (merged ? ntail_ : 0));
-      if (fin1_in_schur)
-        LaunchSUnpackFinK(pg, stream_, d, (const int32_t*)work_i_.ptr, (const int32_t*)pack_off_.ptr, npanel,
-                          Spk_.ptr);
-      else
-        LaunchSPackK(pg, stream_, S_.ptr, n_, (const int32_t*)work_i_.ptr, (const int32_t*)pack_off_.ptr, npanel,
-                     Spk_.ptr, 1);
-      TimedLaunchEnd(kKXchg);
-      if (merged && !fin1_in_schur) {
-        TimedLaunchBegin(kKCamFinal);
-        LaunchCamFinalizeK(stream_, d, 2, 0);
-        TimedLaunchEnd(kKCamFinal);
-      }
-    }
-    TimedLaunchBegin(kKChol);
-    if (chol_.tiles)
-      LaunchCholTiles(d.stamps != nullptr, dim3(chol_.nd > 0 ? 2 : 1), d,
-                      (chol_.cand_lds ? 2 : 0) | (chol_force_tmo_ ? 4 : 0) | (zpre ? 16 : 0) | (stile ? 32 : 0) | chol_delay_);
-    else if (chol_.window)
-      LaunchCholWindowK(d.stamps != nullptr, stream_, d, (const int32_t*)work_i_.ptr, rdg_.ptr);
-    else
-      LaunchCholGlobalK(chol_.gstage, (size_t)std::max(n_, 1) * 8 * (chol_.gstage ? 1 + kCholNb : 1), stream_, d,
-                        (const int32_t*)work_i_.ptr, rdg_.ptr);
-    TimedLaunchEnd(kKChol);
-    if (nk_) LaunchIntrStepK(stream_, d);
-    TimedLaunchBegin(kKPointUpd);
-    if (spec_) {
-      LaunchUpdateLin(d);
-    } else {
-      LaunchPointUpdateK(std::max(wk_.npu, 1), stream_, d);
-    }
-    TimedLaunchEnd(kKPointUpd);
-    const bool multi = comm_ && comm_->nranks() > 1;
-    // the candidate's camera blocks and linearization scalars beside the update scalars, one launch; on one rank
-    // (no free intrinsics, no forced merged chain) the decision too
-    const bool decide_in_reduce = !multi && nk_ == 0 && merge_ != 2;
-    TimedLaunchBegin(kKUpdRed);
-    if (spec_)
-      LaunchCamReduceK(NB_ + 2, stream_, d, decide_in_reduce ? 2 : 1);
-    else
-      LaunchUpdReduceK(stream_, d, multi ? 0 : 1);
-    TimedLaunchEnd(kKUpdRed);
-    if (multi) AllReduceSum(xchg_upd_.ptr, kUNum);
-    if (spec_) {
-      pending_decision_ = !decide_in_reduce;
-    } else if (multi) {
-      TimedLaunchBegin(kKDecide);
-      LaunchDecideK(stream_, d, 0);
-      TimedLaunchEnd(kKDecide);
-    }
+    pending_decision_ = step.pending_out;
+    chol_stile_last_ = step.stile;
   }
-  // a batch leaves no decision pending: the host's state reads and downloads see the decided step
-  if (pending_decision_) {
-    TimedLaunchBegin(kKDecide);
-    LaunchDecideK(stream_, d, 1);
-    TimedLaunchEnd(kKDecide);
-    pending_decision_ = false;
-  }
+  run(PlanBatchTail(pending_decision_));
+  pending_decision_ = false;
   SG_HIP_CHECK(hipGetLastError());
 }
 
@@ -1216,7 +1174,7 @@ int BaSolver::KernelWork(double* bytes, double* flops, int max) {
   by[kKSchur] = M * (jrec - 16 + 4) + P * (80 + 32 + 32 + 8 + 32 + 80 + 32);
   fl[kKSchur] = 2048.0 * wk_.schur_mfma + 512.0 * wk_.schur_rhs;   // 16x16x4 tile updates, 4x4x4 (4-block) rhs slots
   by[kKPointUpd] = M * (jrec + 16 + 4) + P * (32 + 32 + 80 + 32 + 32);
-  if (spec_) {   // k_update_lin: the update's traffic plus the candidate's linearization (a second J record, V, g)
+  if (knobs_.spec) {   // k_update_lin: the update's traffic plus the candidate's linearization (a second J record, V, g)
     by[kKPointUpd] = M * (jrec + jrec + 16 + 4 + 4 + 4) + P * (32 + 32 + 80 + 32 + 32 + 80 + 32) + NB * kCamV * 8;
     fl[kKPointUpd] = M * 420.0;
   }

@@ -773,3 +773,35 @@ def test_rccl_communicator_on_one_rank(gpu_lib, monkeypatch):
     assert s0 == s1
     np.testing.assert_array_equal(p0.q, p1.q)
     np.testing.assert_array_equal(p0.X, p1.X)
+
+
+@pytest.mark.parametrize("env,first,decide,exchange", [
+    ({}, 1, 0, 0),
+    ({"SG_SPEC": "0"}, 4, 0, 0),
+    ({"SG_XCHG_MERGE": "force"}, 1, 4, 3),
+    ({"SG_PACK_S": "1"}, 1, 0, 4),
+], ids=["default", "two_pass", "merged", "packed"])
+def test_iteration_chain_makes_the_planned_launches(gpu_lib, monkeypatch, env, first, decide, exchange):
+    """The launches the driver makes for iterate(1) + iterate(3) on one rank, counted by the kernel timers, against
+    the chain ba_chain.cpp plans (tests/native/chain_plan_check.cpp has the sequences).  Every iteration has one
+    k_schur, k_S_reduce, Cholesky, point pass and closing reduce.  k_linearize, the opening k_cam_reduce and a
+    k_cam_finalize launch of their own belong to a solve's first iteration only (speculative chain: later the
+    finalize pass runs inside k_schur, or, merged, inside k_schur and the unpack), to every iteration with SG_SPEC=0.
+    The forced merged chain leaves each step's decision pending: k_decide opens the third and fourth iteration and
+    closes both batches (4), and the exchange runs in the three merged iterations (a solve's first is unmerged).
+    SG_PACK_S adds the exchange to all four."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    m = make_scene(num_frames=8, num_points=60, seed=3)
+    g = ba.BundleAdjuster()
+    g.load(ba.problem_from_map_frames(m, 6, 8, 2.0))
+    assert g.info()["cholesky_path"] == 0
+    g.set_timing(True)
+    g.begin(default_solver_options(max_num_iterations=10 ** 6, disable_termination=1))
+    g.iterate(1)
+    g.iterate(3)
+    g.sync()
+    counts = {k: c for k, (_, c) in g.kernel_times().items()}
+    g.close()
+    assert counts == {"linearize": first, "cam_reduce": first, "cam_finalize": first, "schur": 4, "S_reduce": 4,
+                      "cholesky": 4, "point_update": 4, "upd_reduce": 4, "decide": decide, "exchange": exchange}
