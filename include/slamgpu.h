@@ -479,6 +479,105 @@ int sg_slam_localize_frames(sg_slam* s, sg_map* map, const int32_t* frames, int3
                             int32_t* obs_inlier /*[map->num_obs], may be NULL*/,
                             sg_solver_summary* summaries /*[n], may be NULL*/);
 
+/* Relative pose of frame pairs: where is frame b relative to frame a, from the pixels they share alone?  Every call
+ * above needs the other half of the map; this one starts a map, or re-joins two frames that share no trusted
+ * landmark.  (The reference never solves this: it starts a frame at the pose of two frames ago, assumes the 150 mm
+ * stereo baseline, main.cpp:496, 540-552, and seeds points at a guessed depth; ApplyEpipolarConstraint only checks
+ * an essential matrix built from poses that exist.)  8-point RANSAC on the device, all listed pairs (a, b) in one
+ * call, pairs[2i] = a, pairs[2i + 1] = b:
+ *   1. Records: the points with an observation with obs_disabled == 0 in a and one in b, in the map order of a's
+ *      observations; where a frame has several enabled observations of the point, the first.  Point flags, point
+ *      locations and both poses are not consulted.  A record is four doubles, the pixel in a then the pixel in b.
+ *      N < 8: SG_REL_DID_NOT_RUN, decided on the host before anything is launched.
+ *   2. Hypotheses: H = max_hypotheses rounded up to a multiple of 256 (anything above 2^20 is taken as 2^20).
+ *      Hypothesis h draws eight distinct record indices, sg_slam_localize_frames' scheme extended: with
+ *      key = a * 65536 + b (map frame indices), base = mix(mix(mix(seed) + key) + h), r_j = mix(base ^ (0x9e3779b9 *
+ *      (j + 1))), i_j = (r_j * (N - j)) >> 32 for j = 0 .. 7, and each i_j is then stepped over the earlier indices
+ *      taken in ascending order (i_j >= p: i_j += 1).  Nothing is carried between hypotheses (csrc/relpose_math.h,
+ *      RelSample).
+ *   3. Minimal solver, fp64: both pixels of each sampled record are undistorted to plane coordinates (Newton on the
+ *      radius, as in sg_slam_triangulate_points); each side gets Hartley's normalisation (centroid to the origin, rms
+ *      distance sqrt 2); the eight epipolar rows x_b' (x) x_a' are summed into the symmetric 9x9 moment matrix M; e is
+ *      the unit eigenvector of its smallest eigenvalue; the 3x3 is de-normalised and projected to singular values
+ *      (1, 1, 0) (EssentialFromMoments).  The eigenvector: L D L^T of M + 2^-40 tr(M) I without pivoting, inverse
+ *      iteration from a fixed start until two iterates agree to 1e-15 in every entry (40 rounds at the most).  l0 and
+ *      l1 come from that iteration and a second, deflated one, l8 from 16 power iterations.  A sample gives no model
+ *      when a value is not finite, a pivot is not positive, the iteration has not converged, or the null direction is
+ *      not determined: (l1 - l0) / l8 <= 1e-12.
+ *   4. Scoring: every E against all N records by the squared Sampson distance in ideal pixels, F = K_b^-T E K_a^-1 on
+ *      the undistorted pixels (fx x + cx, fy y + cy).  MSAC cost = sum of min(e^2, tau^2), formed as T tau^2 + s: T
+ *      the truncated records (a non-finite e^2 counts as truncated), s the sum of e^2 over the others in index order.
+ *      The winner and every tie-break are sg_slam_localize_frames' (step 4 there); the root index is always 0.
+ *      The hypotheses are ranked by that index-order sum.  The figures reported for the winner and compared in step
+ *      6 (msac_cost, ransac_cost, inlier_rms_px) come from a fixed-order workgroup reduction instead: thread t of
+ *      256 sums records t, t + 256, ... in index order, then the 64 lanes of a wave and the four waves are summed
+ *      in a fixed order.  They are reproducible bit for bit and can differ from the index-order sum in the last bits.
+ *   5. Pose: the four decompositions (R1, +u3), (R1, -u3), (R2, +u3), (R2, -u3) of the winner (R1 = U W V^T,
+ *      R2 = U W^T V^T, det +1) are each tested on its inliers: the two depths of d_b f_b = d_a R f_a + t by the 2x2
+ *      least squares of the bearings f = (x, y, 1); a record is in front when both are positive.  The most in-front
+ *      inliers win, ties to the earlier.  Output in the map's convention p = q (X - t): q_rel with
+ *      p_b = q_rel (p_a - t_rel), unit, w >= 0, Eigen memory; t_rel the centre of b in a's camera coordinates, of unit
+ *      length (scale is not observable).  A record's parallax is the angle between R f_a and f_b.  E is reported
+ *      with the sign that makes it [t]x R of that decomposition (t = -R t_rel).
+ *   6. Local optimisation (refine != 0, at most two rounds): EssentialFromMoments on the moments of all current
+ *      inliers (normalised over them), summed by a fixed-order workgroup reduction; all N records are re-scored; the
+ *      result is kept only when its MSAC key is not after the current one in step 4's order (the second round is
+ *      skipped when the first was not kept).  refined reports the rounds kept.  Fewer than 8 inliers: no round.
+ *   7. Status: the first of sg_rel_status' rules that applies, in the order of the enum below.
+ *   8. solved[i] = 1 exactly for SG_REL_OK.  With baseline > 0, frame b of an OK pair is written from frame a's pose
+ *      as it was at entry: q_b = q_rel (x) q_a renormalised with w >= 0, t_b = t_a + baseline R_a^T t_rel; nothing
+ *      else of the map is written.  With baseline == 0 the map is not written.  A failing call writes nothing.
+ *   - SG_EINVAL: a null s, map or options; n < 0; threshold_px <= 0 or NaN; max_hypotheses <= 0; baseline < 0 or NaN;
+ *     a frame index out of range; a == b; the same b listed twice; frames on cameras whose intrinsics cannot both be
+ *     read (frame_camera out of range, or no k); record arrays asked for with rec_capacity below the call's records.
+ *     All of these are found on the host before the device is touched.  n == 0 returns SG_OK before the handle or
+ *     the device is touched.
+ * results (may be NULL) receives each pair's sg_relpose_result.  rec_offset (may be NULL, [n + 1]) receives the
+ * pairs' record ranges; rec_inlier (may be NULL, [rec_capacity]) per record 1 or 0 for OK pairs and -1 elsewhere;
+ * rec_obs (may be NULL, [2 rec_capacity]) per record its map observation index in a, then in b, so that a caller can
+ * disable the outliers.  The call's records never exceed the sum over the pairs of a's observations.
+ * sg_slam_iterations, sg_slam_error and sg_slam_last_summary do not move.  No communicator is involved: rank-local.
+ * Not in scope: the 5-point solver; planar or homography model selection (the 8-point is degenerate when every record
+ * lies on one plane: such a pair gives SG_REL_NO_MODEL or an unreliable pose); a non-linear 5-DoF polish; adaptive
+ * termination; any change to obs_disabled. */
+enum sg_rel_status {
+  SG_REL_OK = 0,
+  SG_REL_DID_NOT_RUN = 1,     /* fewer than 8 records (decided before anything is launched) */
+  SG_REL_NO_MODEL = 2,        /* no hypothesis gave an essential matrix */
+  SG_REL_FEW_INLIERS = 3,     /* fewer than max(min_inliers, 8) inliers */
+  SG_REL_NO_CHEIRALITY = 4,   /* the best decomposition has fewer than max(min_inliers, 8) in-front inliers */
+  SG_REL_LOW_PARALLAX = 5     /* min_parallax > 0 and fewer than max(min_inliers, 8) in-front inliers with
+                                 parallax >= min_parallax: the pure-rotation guard */
+};
+
+typedef struct sg_relpose_options {
+  double threshold_px;      /* tau: inlier threshold and MSAC truncation, ideal px; > 0 */
+  int32_t max_hypotheses;   /* > 0; rounded up to a multiple of 256 */
+  int32_t min_inliers;
+  double min_parallax;      /* rad; 0 = no gate */
+  uint32_t seed;
+  int32_t refine;           /* != 0: local optimisation */
+  double baseline;          /* > 0: write frame b at this distance from a; 0: do not write the map */
+} sg_relpose_options;
+
+typedef struct sg_relpose_result {
+  int32_t status, num_obs;               /* enum sg_rel_status; records N */
+  int32_t num_inliers, num_front, num_parallax, refined;
+  int32_t best_hypothesis;               /* the winner's h; -1 without a model */
+  int32_t best_sample[8];                /* its record indices within the pair, in draw order; -1 without a model */
+  int32_t hypotheses, models;            /* H; hypotheses that produced a model */
+  double msac_cost, ransac_cost;         /* at the reported E; at the RANSAC winner */
+  double inlier_rms_px;
+  double q[4], t[3], E[9];               /* q_rel, t_rel; E row-major, Frobenius norm sqrt 2; zeros without a model */
+} sg_relpose_result;
+
+void sg_relpose_options_default(sg_relpose_options* o);   /* 2.0, 1024, 16, 0, seed 0, refine = 1, baseline = 0 */
+int sg_slam_relative_poses(sg_slam* s, sg_map* map, const int32_t* pairs /*[2n]*/, int32_t n,
+                           const sg_relpose_options* options, int32_t* solved /*[n]*/,
+                           sg_relpose_result* results /*[n], may be NULL*/, int32_t* rec_offset /*[n+1], may be NULL*/,
+                           int32_t* rec_inlier /*[rec_capacity], may be NULL*/,
+                           int32_t* rec_obs /*[2 rec_capacity], may be NULL*/, int32_t rec_capacity);
+
 /* ------------------------------------------------------------------------------------------------
  * Front end: HessianTracker (hessian.h:9-270) and the forward/backward matching step of Matcher
  * (matcher.cpp:173-206 TrackFeature, 247-251 the 3 -> 6 level retry).  A tracker holds `max_images`

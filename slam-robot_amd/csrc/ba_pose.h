@@ -52,6 +52,25 @@ struct LocOut {
 };
 static_assert(sizeof(LocOut) == 112, "written by k_pose_select as 9 doubles and 10 ints");
 
+// The order of the poses of one frame: the MSAC cost T tau^2 + s as a double (T the truncated records, s the sum of
+// e^2 over the inliers); then, among equal doubles, more inliers, then the smaller s; then the smaller h, then the
+// smaller root index.  The two middle keys matter on clean data with outliers present, where every all-inlier
+// sample's s (1e-20 px^2) vanishes in the rounding of T tau^2 + s and the rounded costs tie; they keep the most
+// accurate of those poses instead of the first.  h = -1 marks "no pose" and is after everything.
+struct LocKey {
+  double cost, s;
+  int inl, h, root;
+};
+__device__ __forceinline__ bool loc_before(const LocKey& a, const LocKey& b) {
+  if (a.h < 0) return false;
+  if (b.h < 0) return true;
+  if (a.cost != b.cost) return a.cost < b.cost;
+  if (a.inl != b.inl) return a.inl > b.inl;
+  if (a.s != b.s) return a.s < b.s;
+  if (a.h != b.h) return a.h < b.h;
+  return a.root < b.root;
+}
+
 class PoseSolver {
  public:
   // stream: the HIP stream to run on (the Slam facade passes its solver's); nullptr: a stream of its own

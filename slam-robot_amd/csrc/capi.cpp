@@ -11,6 +11,7 @@
 
 #include "ba_points.h"
 #include "ba_pose.h"
+#include "ba_relpose.h"
 #include "ba_solver.h"
 #include "comm.h"
 #include "common.h"
@@ -29,6 +30,7 @@ struct sg_slam {
   std::unique_ptr<sg::MapOps> mapops;   // created on first use
   std::unique_ptr<sg::PoseSolver> pose;  // created on first use (sg_slam_solve_frame_poses)
   std::unique_ptr<sg::PointSolver> points;   // created on first use (sg_slam_solve_points)
+  std::unique_ptr<sg::RelPoseSolver> relpose;   // created on first use (sg_slam_relative_poses)
   sg_device_options dev;
   sg_solver_options options;
   int32_t iterations = 0;    // Slam::iterations_ (slam.cpp:517)
@@ -422,6 +424,42 @@ int sg_slam_debug_pose_kernel_ms(sg_slam* s, double* ms) {
   SG_CAPI_BEGIN
   SG_REQUIRE(s && ms, SG_EINVAL, "null argument");
   *ms = PoseSolverOf(s).last_kernel_ms();
+  SG_CAPI_END
+}
+
+static sg::RelPoseSolver& RelPoseSolverOf(sg_slam* s) {
+  if (!s->relpose) s->relpose.reset(new sg::RelPoseSolver(s->dev, s->solver->stream()));   // one stream per Slam object
+  return *s->relpose;
+}
+
+int sg_slam_relative_poses(sg_slam* s, sg_map* map, const int32_t* pairs, int32_t n, const sg_relpose_options* options,
+                           int32_t* solved, sg_relpose_result* results, int32_t* rec_offset, int32_t* rec_inlier,
+                           int32_t* rec_obs, int32_t rec_capacity) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s && map && options, SG_EINVAL, "null argument");
+  sg::RelPlan plan;
+  sg::PlanRelPoses(map, pairs, n, options, &plan);   // every argument check, on the host
+  if (n == 0) return SG_OK;   // nothing to solve: neither the handle nor the device is touched
+  SG_REQUIRE(solved, SG_EINVAL, "null result array");
+  SG_REQUIRE(!(rec_inlier || rec_obs) || rec_capacity >= plan.off[n], SG_EINVAL,
+             "rec_capacity is below the call's records");
+  RelPoseSolverOf(s).Solve(map, plan, n, *options, solved, results, rec_offset, rec_inlier, rec_obs);
+  SG_CAPI_END
+}
+
+// Diagnostics (not in the public header): HIP-event time of sg_slam_relative_poses' two launches
+// (tools/relpose_bench.py).
+int sg_slam_debug_relpose_timing(sg_slam* s, int32_t enable) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s, SG_EINVAL, "null handle");
+  RelPoseSolverOf(s).SetTiming(enable != 0);
+  SG_CAPI_END
+}
+
+int sg_slam_debug_relpose_kernel_ms(sg_slam* s, double* ms) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s && ms, SG_EINVAL, "null argument");
+  *ms = RelPoseSolverOf(s).last_kernel_ms();
   SG_CAPI_END
 }
 

@@ -282,6 +282,16 @@ void sg_localize_options_default(sg_localize_options* o) {
   o->range = 2.0;          // main.cpp's CauchyLoss range
 }
 
+void sg_relpose_options_default(sg_relpose_options* o) {
+  o->threshold_px = 2.0;
+  o->max_hypotheses = 1024;
+  o->min_inliers = 16;
+  o->min_parallax = 0.0;
+  o->seed = 0;
+  o->refine = 1;
+  o->baseline = 0.0;
+}
+
 void sg_device_options_default(sg_device_options* o) {
   o->device = 0;
   o->precision = 0;

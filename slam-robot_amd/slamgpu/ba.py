@@ -314,6 +314,51 @@ class Slam:
         localized frames at the written pose, -1 everywhere else."""
         return np.array(getattr(self, "_localization_inliers", np.zeros(0, dtype=np.int32)))
 
+    def RelativePoses(self, m: MapArrays, pairs, threshold_px: float = 2.0, max_hypotheses: int = 1024,
+                      min_inliers: int = 16, min_parallax: float = 0.0, seed: int = 0, refine: bool = True,
+                      baseline: float = 0.0) -> list:
+        """Relative pose of frame pairs (sg_slam_relative_poses): for each listed pair (a, b), where b is relative to
+        a, from the pixels of the points both observe alone, by 8-point RANSAC on the device (max_hypotheses
+        eight-record samples per pair, MSAC on the Sampson distance at threshold_px, local optimisation with refine).
+        Neither pose and no point is read.  With baseline > 0, frame b of each solved pair is written into m.q / m.t
+        at that distance from a's pose as it was at entry; with 0 the map is left alone.  Returns one bool per pair;
+        relative_pose_results() has the statuses, q_rel, the unit t_rel and E, relative_pose_records() the per-record
+        inlier mask and observation indices."""
+        from .capi import SgRelposeOptions, SgRelposeResult
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        n = len(pr)
+        solved = np.zeros(n, dtype=np.int32)
+        res = (SgRelposeResult * max(n, 1))()
+        in_range = (pr[:, 0] >= 0) & (pr[:, 0] < m.num_frames)
+        cap = int(np.bincount(m.obs_frame, minlength=max(m.num_frames, 1))[pr[in_range, 0]].sum()) if n else 0
+        off = np.zeros(n + 1, dtype=np.int32)
+        inl = np.full(max(cap, 1), -1, dtype=np.int32)
+        obs = np.full(2 * max(cap, 1), -1, dtype=np.int32)
+        opt = SgRelposeOptions(threshold_px=threshold_px, max_hypotheses=max_hypotheses, min_inliers=min_inliers,
+                               min_parallax=min_parallax, seed=seed, refine=int(bool(refine)), baseline=baseline)
+        ms = m.struct()
+        ip = C.POINTER(C.c_int32)
+        check(self.lib.sg_slam_relative_poses(self.h, C.byref(ms), pr.ctypes.data_as(ip), n, C.byref(opt),
+                                              solved.ctypes.data_as(ip), res, off.ctypes.data_as(ip),
+                                              inl.ctypes.data_as(ip), obs.ctypes.data_as(ip), cap),
+              "Slam::RelativePoses")
+        self._relpose_results = [res[i].as_dict() for i in range(n)]
+        total = int(off[n])
+        self._relpose_records = (off, inl[:total].copy(), obs[:2 * total].reshape(-1, 2).copy())
+        return [bool(v) for v in solved]
+
+    def relative_pose_results(self) -> list:
+        """Result dicts of the last RelativePoses call, one per pair: status (a REL_STATUS name), num_obs,
+        num_inliers, num_front, num_parallax, refined, best_hypothesis, best_sample, hypotheses, models, msac_cost,
+        ransac_cost, inlier_rms_px, q, t and E (3 x 3)."""
+        return list(getattr(self, "_relpose_results", []))
+
+    def relative_pose_records(self) -> tuple:
+        """(offsets [n + 1], inlier mask per record: 1 / 0 for solved pairs and -1 elsewhere, observation indices
+        per record: in a, in b) of the last RelativePoses call."""
+        return getattr(self, "_relpose_records", (np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32),
+                                                  np.zeros((0, 2), dtype=np.int32)))
+
     def SolvePoints(self, m: MapArrays, points, range_: float) -> list:
         """Structure-only bundle adjustment (sg_slam_solve_points): each listed point's location against the map's
         frames as they are, all points in one device launch.  Point flags are not consulted.  Updates m.X of the

@@ -118,6 +118,29 @@ class SgLocalizeResult(C.Structure):
         return d
 
 
+REL_STATUS = {0: "OK", 1: "DID_NOT_RUN", 2: "NO_MODEL", 3: "FEW_INLIERS", 4: "NO_CHEIRALITY", 5: "LOW_PARALLAX"}
+
+
+class SgRelposeOptions(C.Structure):
+    _fields_ = [("threshold_px", C.c_double), ("max_hypotheses", C.c_int32), ("min_inliers", C.c_int32),
+                ("min_parallax", C.c_double), ("seed", C.c_uint32), ("refine", C.c_int32), ("baseline", C.c_double)]
+
+
+class SgRelposeResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("num_obs", C.c_int32), ("num_inliers", C.c_int32), ("num_front", C.c_int32),
+                ("num_parallax", C.c_int32), ("refined", C.c_int32), ("best_hypothesis", C.c_int32),
+                ("best_sample", C.c_int32 * 8), ("hypotheses", C.c_int32), ("models", C.c_int32),
+                ("msac_cost", C.c_double), ("ransac_cost", C.c_double), ("inlier_rms_px", C.c_double),
+                ("q", C.c_double * 4), ("t", C.c_double * 3), ("E", C.c_double * 9)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["status"] = REL_STATUS.get(self.status, "?")
+        d["best_sample"] = tuple(self.best_sample[:])
+        d["q"], d["t"], d["E"] = np.array(self.q[:]), np.array(self.t[:]), np.array(self.E[:]).reshape(3, 3)
+        return d
+
+
 class SgBaInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("num_frames", "num_points", "num_obs", "num_blocks", "n", "band_tiles",
                                          "cholesky_path", "num_pairs", "rank", "nranks", "cholesky_split",
@@ -363,6 +386,9 @@ SYMBOLS = {
     "sg_localize_options_default": (None, [C.POINTER(SgLocalizeOptions)]),
     "sg_slam_localize_frames": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32, C.POINTER(SgLocalizeOptions),
                                           _ip, C.POINTER(SgLocalizeResult), _ip, C.POINTER(SgSolverSummary)]),
+    "sg_relpose_options_default": (None, [C.POINTER(SgRelposeOptions)]),
+    "sg_slam_relative_poses": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32, C.POINTER(SgRelposeOptions), _ip,
+                                         C.POINTER(SgRelposeResult), _ip, _ip, _ip, C.c_int32]),
     "sg_triangulate_options_default": (None, [C.POINTER(SgTriangulateOptions)]),
     "sg_slam_triangulate_points": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32,
                                              C.POINTER(SgTriangulateOptions), _ip, C.POINTER(SgTriangulateResult),
