@@ -578,6 +578,110 @@ int sg_slam_relative_poses(sg_slam* s, sg_map* map, const int32_t* pairs /*[2n]*
                            int32_t* rec_inlier /*[rec_capacity], may be NULL*/,
                            int32_t* rec_obs /*[2 rec_capacity], may be NULL*/, int32_t rec_capacity);
 
+/* Alignment of matched landmarks: which similarity joins two pieces of one map?  After a revisit ("Consider loop
+ * closing when adding new points", main.cpp:5), or when a map restarted with sg_slam_relative_poses has to be put back
+ * into the old one, the same landmarks stand twice in one sg_map, in two coordinate systems that differ by a rotation,
+ * a translation and a scale (a monocular restart has no scale; a long stereo run drifts).  The Hamming matcher
+ * delivers the landmark-to-landmark matches, wrong pairs included; this call turns them into the transform
+ * Y = scale R(q) X + t from the a side to the b side, by 3-point Sim(3) RANSAC on the device, and
+ * sg_map_apply_similarity applies it.  All groups of a call run in two launches.  Per group g, over the
+ * correspondences corr[2 j], corr[2 j + 1] (point a, point b; map point indices), j in
+ * [group_offset[g], group_offset[g + 1]):
+ *   1. Records: a correspondence becomes a record when both points are slam-usable (none of the flags BAD_LOCATION,
+ *      NO_BASELINE, NO_OBSERVATIONS, BAD_FEATURE, the filter of sg_slam_solve_frame_poses), all eight doubles of the two
+ *      locations are finite and |W| >= 1e-9 |X|_2 on both sides.  A record is six doubles, X_a.xyz / X_a.w then
+ *      X_b.xyz / X_b.w, in listed order; N of them.  N < 4: SG_ALIGN_DID_NOT_RUN, decided on the host before anything is
+ *      launched.  The map's frames, observations and pixels are not read.
+ *   2. Hypotheses: H = max_hypotheses rounded up to a multiple of 256 (anything above 2^20 is taken as 2^20).
+ *      Hypothesis h draws three distinct record indices exactly as in sg_slam_localize_frames step 2 (PnpSample), with
+ *      the map index of point a of the group's first listed correspondence in the place of the frame index: the
+ *      result does not depend on the group's position in the call.
+ *   3. Minimal solver, fp64, Horn's closed form (csrc/align_math.h); the same function serves three records and all
+ *      inliers.  Centroids xm, ym, centred x', y', S_ab = sum x'_a y'_b; the symmetric 4x4 N in (w, x, y, z) order
+ *          row 0:      Sxx+Syy+Szz, Syz-Szy, Szx-Sxz, Sxy-Syx
+ *          diagonal:   Sxx-Syy-Szz, -Sxx+Syy-Szz, -Sxx-Syy+Szz
+ *          the rest:   N12 = Sxy+Syx, N13 = Szx+Sxz, N23 = Syz+Szy;
+ *      q is the unit eigenvector of N's largest eigenvalue l3 (cyclic Jacobi, sg_slam_triangulate_points' TriJacobi4,
+ *      on -N); gap = (l3 - l2) / l3 with l2 the next eigenvalue, which is 2 (s2 + s3) / (s1 + s2 + s3) in the singular
+ *      values of S for a proper match: 0 for collinear points, of order one for a spread set.
+ *      scale = sqrt(sum |y'|^2 / sum |x'|^2), or 1 with fix_scale; t = ym - scale R xm.  No model when a value is not
+ *      finite, sum |x'|^2 or sum |y'|^2 is 0, l3 <= 0, gap <= 1e-12, or scale is outside [1 / max_scale, max_scale]
+ *      (max_scale == 0: no gate).
+ *   4. Scoring: e^2 = |Y - (scale R X + t)|^2, in b's coordinates, against all N records.  MSAC cost = sum of
+ *      min(e^2, tau^2), tau = threshold, formed as T tau^2 + s exactly as in sg_slam_localize_frames step 4: T the
+ *      truncated records (a non-finite e^2 counts as truncated), s the sum of e^2 over the others in index order.  The
+ *      winner and every tie-break are that step's (more inliers, then the smaller s, then the smaller h); the root
+ *      index is always 0.  The hypotheses are ranked by the index-order sum; the figures reported for the winner and
+ *      compared in step 5 (msac_cost, ransac_cost, inlier_rms) come from the fixed-order workgroup reduction of
+ *      sg_slam_relative_poses step 4 (thread t of 256 sums records t, t + 256, ..., then the lanes and the waves in a
+ *      fixed order): reproducible bit for bit, and they can differ from the index-order sum in the last bits.
+ *   5. Local optimisation (refine != 0, at most two rounds, needs at least 4 inliers): step 3 on all current inliers
+ *      (e^2 <= tau^2), by two fixed-order workgroup reductions, the centroids first and then the centred moments
+ *      (never raw second moments: map coordinates are thousands of units against spreads of hundreds); all N records
+ *      are re-scored; the result is kept only when its MSAC key is not after the current one in step 4's order (the
+ *      second round is skipped when the first was not kept).  refined reports the rounds kept.
+ *   6. Status: the first of sg_align_status' rules that applies, in the order of the enum below.  gap is always that
+ *      of the N matrix of the final inliers (those of the reported transform), with refine == 0 too, and 0 where that
+ *      matrix gives no finite value; gap < min_gap: SG_ALIGN_DEGENERATE (the inliers are collinear to that degree and
+ *      do not fix the rotation about their line).
+ *   7. solved[g] = 1 exactly for SG_ALIGN_OK.  corr_inlier (may be NULL, one int per correspondence of the call) is 1
+ *      or 0 for each record of an OK group at the reported transform, and -1 for correspondences that are no records
+ *      and for groups that are not OK.  The map is never written by this call; sg_slam_iterations, sg_slam_error and
+ *      sg_slam_last_summary do not move.  No communicator is involved: rank-local on a sharded handle.
+ *   - SG_EINVAL, all found on the host before the device is touched: a null s, map or options; n < 0; with n > 0 a null
+ *     group_offset or solved, and a null corr when the call lists a correspondence; group_offset[0] != 0 or a
+ *     decreasing offset; a point index out of range; a correspondence with a == b; threshold <= 0 or NaN;
+ *     max_hypotheses <= 0; min_gap < 0 or NaN; max_scale neither 0 nor >= 1.  n == 0 returns SG_OK before the handle or
+ *     the device is touched.  A failing call writes nothing.
+ * results (may be NULL) receives each group's sg_align_result.
+ * Not in scope: scoring by reprojection in the frames or depth-weighted thresholds; adaptive termination; merging the
+ * duplicated landmarks or their observations; pose-graph optimisation; any change to obs_disabled or point flags. */
+enum sg_align_status {
+  SG_ALIGN_OK = 0,
+  SG_ALIGN_DID_NOT_RUN = 1,   /* fewer than 4 records (decided on the host, before any launch) */
+  SG_ALIGN_NO_MODEL = 2,      /* no hypothesis gave a finite transform inside the scale gate */
+  SG_ALIGN_FEW_INLIERS = 3,   /* fewer than max(min_inliers, 4) inliers */
+  SG_ALIGN_DEGENERATE = 4     /* the inliers do not fix the rotation: gap < min_gap (collinear landmarks) */
+};
+
+typedef struct sg_align_options {
+  double threshold;         /* tau: inlier threshold and MSAC truncation, map units; > 0 */
+  int32_t max_hypotheses;   /* > 0; rounded up to a multiple of 256 */
+  int32_t min_inliers;
+  uint32_t seed;
+  int32_t refine;           /* != 0: local optimisation, at most two rounds */
+  int32_t fix_scale;        /* != 0: scale = 1 (rigid alignment, for maps whose scale the stereo baseline fixes) */
+  double max_scale;         /* 0: no gate; otherwise >= 1: a transform with scale outside [1 / max_scale, max_scale]
+                               is no model */
+  double min_gap;           /* >= 0 */
+} sg_align_options;
+
+typedef struct sg_align_result {
+  int32_t status, num_corr, num_records, num_inliers, refined;   /* enum sg_align_status; listed; records N */
+  int32_t best_hypothesis, best_sample[3];   /* the winner's h and record indices in draw order; -1 without a model */
+  int32_t hypotheses, models;                /* H; hypotheses that produced a model */
+  double msac_cost, ransac_cost, inlier_rms, gap;   /* at the reported transform; at the RANSAC winner */
+  double scale, q[4], t[3];   /* Y = scale R(q) X + t; q unit, Eigen [x,y,z,w], w >= 0; zeros without a model */
+} sg_align_result;
+
+void sg_align_options_default(sg_align_options* o);   /* 10.0, 1024, 8, seed 0, refine 1, fix_scale 0, max_scale 0, min_gap 1e-6 */
+int sg_slam_align_points(sg_slam* s, sg_map* map, const int32_t* corr /*[2M]: point a, point b*/,
+                         const int32_t* group_offset /*[n+1]*/, int32_t n, const sg_align_options* options,
+                         int32_t* solved /*[n]*/, sg_align_result* results /*[n], may be NULL*/,
+                         int32_t* corr_inlier /*[M], may be NULL*/);
+
+/* Applies the similarity Y = scale R(q) X + t to the listed frames and points of the map: the companion that makes a
+ * loop correction one call after sg_slam_align_points.  Host only: no handle, no device.
+ *   - each listed point: X <- [scale R X.xyz + t X.w, X.w], not renormalised;
+ *   - each listed frame: t_f <- scale R t_f + t and q_f <- q_f (x) conj(q), renormalised with w >= 0.  Under the map's
+ *     convention p = q_f (X - t_f) every camera-space point of a transformed frame on a transformed point is scaled by
+ *     scale, so every pixel is unchanged.
+ * q is normalised before use.  SG_EINVAL, with nothing written: a null map, q or t, or a null list with a positive
+ * count; a negative count; q with | |q|^2 - 1 | > 1e-9 (zero and non-finite included); scale <= 0 or not finite; a
+ * non-finite t; an index out of range or listed twice. */
+int sg_map_apply_similarity(sg_map* map, double scale, const double* q /*[4]*/, const double* t /*[3]*/,
+                            const int32_t* frames /*[nf]*/, int32_t nf, const int32_t* points /*[np]*/, int32_t np);
+
 /* ------------------------------------------------------------------------------------------------
  * Front end: HessianTracker (hessian.h:9-270) and the forward/backward matching step of Matcher
  * (matcher.cpp:173-206 TrackFeature, 247-251 the 3 -> 6 level retry).  A tracker holds `max_images`

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <memory>
 
+#include "ba_align.h"
 #include "ba_points.h"
 #include "ba_pose.h"
 #include "ba_relpose.h"
@@ -31,6 +32,7 @@ struct sg_slam {
   std::unique_ptr<sg::PoseSolver> pose;  // created on first use (sg_slam_solve_frame_poses)
   std::unique_ptr<sg::PointSolver> points;   // created on first use (sg_slam_solve_points)
   std::unique_ptr<sg::RelPoseSolver> relpose;   // created on first use (sg_slam_relative_poses)
+  std::unique_ptr<sg::AlignSolver> align;   // created on first use (sg_slam_align_points)
   sg_device_options dev;
   sg_solver_options options;
   int32_t iterations = 0;    // Slam::iterations_ (slam.cpp:517)
@@ -460,6 +462,40 @@ int sg_slam_debug_relpose_kernel_ms(sg_slam* s, double* ms) {
   SG_CAPI_BEGIN
   SG_REQUIRE(s && ms, SG_EINVAL, "null argument");
   *ms = RelPoseSolverOf(s).last_kernel_ms();
+  SG_CAPI_END
+}
+
+static sg::AlignSolver& AlignSolverOf(sg_slam* s) {
+  if (!s->align) s->align.reset(new sg::AlignSolver(s->dev, s->solver->stream()));   // one stream per Slam object
+  return *s->align;
+}
+
+int sg_slam_align_points(sg_slam* s, sg_map* map, const int32_t* corr, const int32_t* group_offset, int32_t n,
+                         const sg_align_options* options, int32_t* solved, sg_align_result* results,
+                         int32_t* corr_inlier) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s && map && options, SG_EINVAL, "null argument");
+  sg::AlignPlan plan;
+  sg::PlanAlign(map, corr, group_offset, n, options, &plan);   // every argument check, on the host
+  if (n == 0) return SG_OK;   // nothing to align: neither the handle nor the device is touched
+  SG_REQUIRE(solved, SG_EINVAL, "null result array");
+  AlignSolverOf(s).Solve(plan, n, group_offset[n], *options, solved, results, corr_inlier);
+  SG_CAPI_END
+}
+
+// Diagnostics (not in the public header): HIP-event time of sg_slam_align_points' two launches
+// (tools/align_bench.py).
+int sg_slam_debug_align_timing(sg_slam* s, int32_t enable) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s, SG_EINVAL, "null handle");
+  AlignSolverOf(s).SetTiming(enable != 0);
+  SG_CAPI_END
+}
+
+int sg_slam_debug_align_kernel_ms(sg_slam* s, double* ms) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s && ms, SG_EINVAL, "null argument");
+  *ms = AlignSolverOf(s).last_kernel_ms();
   SG_CAPI_END
 }
 

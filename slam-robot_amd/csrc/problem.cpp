@@ -5,6 +5,7 @@
 // a LocalMap, producing the sg_problem the device solver consumes.  Ceres keeps pointers into the map;
 // here the solved blocks are copied back by sg_problem_write_back (same observable effect).
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <numeric>
@@ -290,6 +291,71 @@ void sg_relpose_options_default(sg_relpose_options* o) {
   o->seed = 0;
   o->refine = 1;
   o->baseline = 0.0;
+}
+
+void sg_align_options_default(sg_align_options* o) {
+  o->threshold = 10.0;
+  o->max_hypotheses = 1024;
+  o->min_inliers = 8;
+  o->seed = 0;
+  o->refine = 1;
+  o->fix_scale = 0;
+  o->max_scale = 0.0;      // no gate
+  o->min_gap = 1e-6;
+}
+
+int sg_map_apply_similarity(sg_map* map, double scale, const double* q, const double* t, const int32_t* frames,
+                            int32_t nf, const int32_t* points, int32_t np) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(map && q && t, SG_EINVAL, "null argument");
+  SG_REQUIRE(nf >= 0 && np >= 0, SG_EINVAL, "negative count");
+  SG_REQUIRE((nf == 0 || frames) && (np == 0 || points), SG_EINVAL, "null index list");
+  SG_REQUIRE(std::isfinite(scale) && scale > 0.0, SG_EINVAL, "scale must be positive and finite");
+  const double n2 = (q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3]);
+  SG_REQUIRE(std::fabs(n2 - 1.0) <= 1e-9, SG_EINVAL, "q is not a unit quaternion");   // (false for NaN)
+  SG_REQUIRE(std::isfinite(t[0]) && std::isfinite(t[1]) && std::isfinite(t[2]), SG_EINVAL, "t is not finite");
+  SG_REQUIRE(map->num_frames >= 0 && map->num_points >= 0, SG_EINVAL, "negative map sizes");
+  SG_REQUIRE((nf == 0 || (map->q && map->t)) && (np == 0 || map->X), SG_EINVAL, "the map's arrays cannot be read");
+  std::vector<uint8_t> seen_f((size_t)map->num_frames, 0), seen_p((size_t)map->num_points, 0);
+  for (int i = 0; i < nf; ++i) {
+    SG_REQUIRE(frames[i] >= 0 && frames[i] < map->num_frames, SG_EINVAL, "frame index out of range");
+    SG_REQUIRE(!seen_f[frames[i]], SG_EINVAL, "frame listed twice");
+    seen_f[frames[i]] = 1;
+  }
+  for (int i = 0; i < np; ++i) {
+    SG_REQUIRE(points[i] >= 0 && points[i] < map->num_points, SG_EINVAL, "point index out of range");
+    SG_REQUIRE(!seen_p[points[i]], SG_EINVAL, "point listed twice");
+    seen_p[points[i]] = 1;
+  }
+  // A = scale R(q), q normalised; R the standard matrix of a unit quaternion in Eigen memory [x, y, z, w]
+  const double in = 1.0 / std::sqrt(n2);
+  const double x = q[0] * in, y = q[1] * in, z = q[2] * in, w = q[3] * in;
+  const double A[9] = {scale * (1.0 - 2.0 * (y * y + z * z)), scale * (2.0 * (x * y - w * z)),
+                       scale * (2.0 * (x * z + w * y)),       scale * (2.0 * (x * y + w * z)),
+                       scale * (1.0 - 2.0 * (x * x + z * z)), scale * (2.0 * (y * z - w * x)),
+                       scale * (2.0 * (x * z - w * y)),       scale * (2.0 * (y * z + w * x)),
+                       scale * (1.0 - 2.0 * (x * x + y * y))};
+  for (int i = 0; i < np; ++i) {
+    double* X = map->X + 4 * (size_t)points[i];
+    const double v[3] = {X[0], X[1], X[2]};
+    for (int r = 0; r < 3; ++r) X[r] = (A[3 * r] * v[0] + A[3 * r + 1] * v[1] + A[3 * r + 2] * v[2]) + t[r] * X[3];
+  }
+  for (int i = 0; i < nf; ++i) {
+    double* tf = map->t + 3 * (size_t)frames[i];
+    double* qf = map->q + 4 * (size_t)frames[i];
+    const double v[3] = {tf[0], tf[1], tf[2]};
+    for (int r = 0; r < 3; ++r) tf[r] = (A[3 * r] * v[0] + A[3 * r + 1] * v[1] + A[3 * r + 2] * v[2]) + t[r];
+    // q_f (x) conj(q): the rotation of conj(q), then that of q_f
+    const double p[4] = {qf[0], qf[1], qf[2], qf[3]}, c[4] = {-x, -y, -z, w};
+    double r4[4] = {p[3] * c[0] + p[0] * c[3] + p[1] * c[2] - p[2] * c[1],
+                    p[3] * c[1] - p[0] * c[2] + p[1] * c[3] + p[2] * c[0],
+                    p[3] * c[2] + p[0] * c[1] - p[1] * c[0] + p[2] * c[3],
+                    p[3] * c[3] - p[0] * c[0] - p[1] * c[1] - p[2] * c[2]};
+    double rn = 1.0 / std::sqrt((r4[0] * r4[0] + r4[1] * r4[1]) + (r4[2] * r4[2] + r4[3] * r4[3]));
+    if (r4[3] < 0.0) rn = -rn;
+    for (int k = 0; k < 4; ++k) qf[k] = r4[k] * rn;
+  }
+  SG_CAPI_END
 }
 
 void sg_device_options_default(sg_device_options* o) {

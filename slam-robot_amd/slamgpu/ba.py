@@ -359,6 +359,56 @@ class Slam:
         return getattr(self, "_relpose_records", (np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32),
                                                   np.zeros((0, 2), dtype=np.int32)))
 
+    def AlignPoints(self, m: MapArrays, groups, threshold: float = 10.0, max_hypotheses: int = 1024,
+                    min_inliers: int = 8, seed: int = 0, refine: bool = True, fix_scale: bool = False,
+                    max_scale: float = 0.0, min_gap: float = 1e-6) -> list:
+        """Alignment of matched landmarks (sg_slam_align_points): for each group, a (K, 2) array of map point indices
+        (point a, point b), the similarity Y = scale R(q) X + t that takes the a side onto the b side, by 3-point
+        Sim(3) RANSAC on the device (max_hypotheses samples per group, MSAC on the distance in b's coordinates at
+        threshold, local optimisation with refine).  The map is not written: ApplySimilarity does that.  Returns one
+        result dict per group: the fields of sg_align_result with status as an ALIGN_STATUS name, "solved", and
+        "inliers", an int32 array per correspondence of the group (1 / 0 for the records of a solved group, -1 for
+        correspondences that were no records and for groups that are not solved)."""
+        from .capi import SgAlignOptions, SgAlignResult
+        gs = [np.ascontiguousarray(g, dtype=np.int32).reshape(-1, 2) for g in groups]
+        n = len(gs)
+        off = np.zeros(n + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(g) for g in gs])
+        total = int(off[n])
+        corr = np.concatenate(gs).reshape(-1) if total else np.zeros(0, dtype=np.int32)
+        solved = np.zeros(n, dtype=np.int32)
+        res = (SgAlignResult * max(n, 1))()
+        inl = np.full(max(total, 1), -1, dtype=np.int32)
+        opt = SgAlignOptions(threshold=threshold, max_hypotheses=max_hypotheses, min_inliers=min_inliers, seed=seed,
+                             refine=int(bool(refine)), fix_scale=int(bool(fix_scale)), max_scale=max_scale,
+                             min_gap=min_gap)
+        ms = m.struct()
+        ip = C.POINTER(C.c_int32)
+        # (corr is passed by address even when empty: only its length decides whether it is read)
+        check(self.lib.sg_slam_align_points(self.h, C.byref(ms), corr.ctypes.data_as(ip), off.ctypes.data_as(ip), n,
+                                            C.byref(opt), solved.ctypes.data_as(ip), res, inl.ctypes.data_as(ip)),
+              "Slam::AlignPoints")
+        out = []
+        for i in range(n):
+            d = res[i].as_dict()
+            d["solved"] = bool(solved[i])
+            d["inliers"] = inl[off[i]:off[i + 1]].copy()
+            out.append(d)
+        return out
+
+    def ApplySimilarity(self, m: MapArrays, scale: float, q, t, frames, points) -> None:
+        """sg_map_apply_similarity: moves the listed frames and points of m through Y = scale R(q) X + t in place (on
+        the host; pixels of moved frames on moved points do not change)."""
+        qq = np.ascontiguousarray(q, dtype=np.float64).reshape(4)
+        tt = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        pt = np.ascontiguousarray(points, dtype=np.int32).reshape(-1)
+        ms = m.struct()
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        check(self.lib.sg_map_apply_similarity(C.byref(ms), float(scale), qq.ctypes.data_as(dp), tt.ctypes.data_as(dp),
+                                               fr.ctypes.data_as(ip), len(fr), pt.ctypes.data_as(ip), len(pt)),
+              "Slam::ApplySimilarity")
+
     def SolvePoints(self, m: MapArrays, points, range_: float) -> list:
         """Structure-only bundle adjustment (sg_slam_solve_points): each listed point's location against the map's
         frames as they are, all points in one device launch.  Point flags are not consulted.  Updates m.X of the

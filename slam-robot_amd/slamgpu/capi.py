@@ -141,6 +141,30 @@ class SgRelposeResult(C.Structure):
         return d
 
 
+ALIGN_STATUS = {0: "OK", 1: "DID_NOT_RUN", 2: "NO_MODEL", 3: "FEW_INLIERS", 4: "DEGENERATE"}
+
+
+class SgAlignOptions(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("max_hypotheses", C.c_int32), ("min_inliers", C.c_int32),
+                ("seed", C.c_uint32), ("refine", C.c_int32), ("fix_scale", C.c_int32), ("max_scale", C.c_double),
+                ("min_gap", C.c_double)]
+
+
+class SgAlignResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("num_corr", C.c_int32), ("num_records", C.c_int32),
+                ("num_inliers", C.c_int32), ("refined", C.c_int32), ("best_hypothesis", C.c_int32),
+                ("best_sample", C.c_int32 * 3), ("hypotheses", C.c_int32), ("models", C.c_int32),
+                ("msac_cost", C.c_double), ("ransac_cost", C.c_double), ("inlier_rms", C.c_double),
+                ("gap", C.c_double), ("scale", C.c_double), ("q", C.c_double * 4), ("t", C.c_double * 3)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["status"] = ALIGN_STATUS.get(self.status, "?")
+        d["best_sample"] = tuple(self.best_sample[:])
+        d["q"], d["t"] = np.array(self.q[:]), np.array(self.t[:])
+        return d
+
+
 class SgBaInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("num_frames", "num_points", "num_obs", "num_blocks", "n", "band_tiles",
                                          "cholesky_path", "num_pairs", "rank", "nranks", "cholesky_split",
@@ -389,6 +413,10 @@ SYMBOLS = {
     "sg_relpose_options_default": (None, [C.POINTER(SgRelposeOptions)]),
     "sg_slam_relative_poses": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32, C.POINTER(SgRelposeOptions), _ip,
                                          C.POINTER(SgRelposeResult), _ip, _ip, _ip, C.c_int32]),
+    "sg_align_options_default": (None, [C.POINTER(SgAlignOptions)]),
+    "sg_slam_align_points": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, _ip, C.c_int32, C.POINTER(SgAlignOptions),
+                                       _ip, C.POINTER(SgAlignResult), _ip]),
+    "sg_map_apply_similarity": (C.c_int, [C.POINTER(SgMap), C.c_double, _dp, _dp, _ip, C.c_int32, _ip, C.c_int32]),
     "sg_triangulate_options_default": (None, [C.POINTER(SgTriangulateOptions)]),
     "sg_slam_triangulate_points": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32,
                                              C.POINTER(SgTriangulateOptions), _ip, C.POINTER(SgTriangulateResult),
