@@ -635,7 +635,7 @@ int sg_slam_relative_poses(sg_slam* s, sg_map* map, const int32_t* pairs /*[2n]*
  *     the device is touched.  A failing call writes nothing.
  * results (may be NULL) receives each group's sg_align_result.
  * Not in scope: scoring by reprojection in the frames or depth-weighted thresholds; adaptive termination; merging the
- * duplicated landmarks or their observations; pose-graph optimisation; any change to obs_disabled or point flags. */
+ * duplicated landmarks or their observations; any change to obs_disabled or point flags. */
 enum sg_align_status {
   SG_ALIGN_OK = 0,
   SG_ALIGN_DID_NOT_RUN = 1,   /* fewer than 4 records (decided on the host, before any launch) */
@@ -681,6 +681,105 @@ int sg_slam_align_points(sg_slam* s, sg_map* map, const int32_t* corr /*[2M]: po
  * non-finite t; an index out of range or listed twice. */
 int sg_map_apply_similarity(sg_map* map, double scale, const double* q /*[4]*/, const double* t /*[3]*/,
                             const int32_t* frames /*[nf]*/, int32_t nf, const int32_t* points /*[np]*/, int32_t np);
+
+/* Pose-graph optimisation: spread a loop closure over the frames.  sg_slam_align_points gives the similarity that
+ * joins two pieces of a map, and sg_map_apply_similarity moves one piece rigidly; but the drift of a long run is not a
+ * rigid offset of one piece.  This call distributes it over the trajectory, scale included, so that the window solve
+ * that follows starts inside its basin.  A call holds any number of graphs, one workgroup each, in one launch; graph g
+ * has the nodes node_offset[g] .. node_offset[g + 1] and the edges edge_offset[g] .. edge_offset[g + 1].
+ *   Nodes.  node_frame[i] is a map frame, node_fixed[i] != 0 holds it constant.  State: q (unit, the map's
+ *     p = R(q)(X - t)), the centre t and the log-scale sigma, 0 for every node at entry; lambda = e^sigma is the local
+ *     map scale at the frame: world-from-camera is p -> lambda R^T p + t.  A free node carries 7 unknowns: the rotation
+ *     by ceres::QuaternionParameterization on Eigen memory (the one sg_slam_solve_frame_poses uses), t and sigma
+ *     additive; with fix_scale 6: sigma stays 0 and the scale residual is dropped.
+ *   Edges.  edge_ab[2 e], edge_ab[2 e + 1] are positions a != b in the graph's node list; edge_meas[8 e ..] is the
+ *     measurement q^ (4), u^ (3), rho^; edge_weight[3 e ..] is w_rot, w_t, w_s (w_s is not read with fix_scale).  The
+ *     residual, in fp64:
+ *         q_e = conj(q^) (x) q_a (x) conj(q_b), sign-flipped to w >= 0;  omega = its rotation vector
+ *         r[0:3] = w_rot omega;  r[3:6] = w_t (e^-sigma_a R_a (t_b - t_a) - u^);  r[6] = w_s (sigma_b - sigma_a - rho^)
+ *     omega = 2 atan2(|v|, w) v / |v| with v the vector part of q_e; where |v|^2 < 1e-8 the factor comes from the series
+ *     (2 / w)(1 - x^2 / 3 + x^4 / 5), x = |v| / w (csrc/posegraph_math.h, with the analytic 7 x 14 Jacobian).
+ *     Loss: range > 0: CauchyLoss(range) on |r|^2 as everywhere else here (residual and Jacobian scaled by sqrt(rho'));
+ *     range == 0: none.  Several edges between one pair are summed in listed order.  An edge between two fixed nodes
+ *     goes into fixed_cost only.
+ *   Solver.  The handle's sg_solver_options (sg_slam_set_options) on the Ceres 1.8 LM of sg_ba_solve: Jacobi scaling
+ *     from iteration 0, the clamped LM diagonal, a sparse block Cholesky of the damped scaled system (a non-positive
+ *     pivot makes an invalid step), the model cost change -sum_e (J_e d).(r_e + J_e d / 2) from the stored edge
+ *     Jacobians, the same step decision.  The elimination order (greedy minimum degree, ties to the lower list
+ *     position), the fill and every summation order are planned on the host (csrc/posegraph_plan.h); the whole LM loop
+ *     of a graph runs in one workgroup of one launch, so a result is reproducible bit for bit and does not depend on
+ *     the graph's position in the call.
+ *   Status per graph, the first rule of sg_posegraph_status that applies.  Anything but SG_PG_OK leaves the graph's
+ *     frames untouched.
+ *   Write-back of an SG_PG_OK graph: q_f normalised with w >= 0 and t_f of its free nodes into the map; log_scale[i]
+ *     (one per listed node of the call) receives sigma, 0 for fixed nodes and for graphs that are not OK.  With
+ *     move_points != 0, on the host: every map point with an observation with obs_disabled == 0 in a node of an OK
+ *     graph moves with its anchor, the node frame of its first such observation in map order:
+ *         xyz <- lambda R_new^T R_old (xyz - W t_old) + W t_new,  W kept, not renormalised
+ *     which leaves every pixel of the anchor frame on that point unchanged (a fixed anchor moves nothing).  Point flags
+ *     and obs_disabled are neither read for gating nor written beyond that test.
+ *   summaries (may be NULL) receives each graph's summary (SG_DID_NOT_RUN where the device did not run it).
+ *     sg_slam_iterations grows by the num_iterations of the graphs that ran, and sg_slam_error / sg_slam_last_summary
+ *     take the values of the last listed graph that ran (the convention of sg_slam_solve_frame_poses).
+ *   - SG_EINVAL, all found on the host before the device is touched, with nothing written: a null s, map or options;
+ *     n < 0; with n > 0 a null node_offset, edge_offset or status, a null node_frame or node_fixed when the call lists a
+ *     node, a null edge_ab, edge_meas or edge_weight when it lists an edge; an offset array that does not start at 0 or
+ *     decreases; a frame index out of range; a frame listed twice in the call; an edge index out of the graph's node
+ *     list; a == b; q^ with | |q^|^2 - 1 | > 1e-9 (zero and non-finite included); a non-finite u^ or rho^; a weight that
+ *     is not > 0 and finite (w_s only without fix_scale); range < 0, NaN or infinite; a map whose poses cannot be read;
+ *     with move_points a map whose points or observations cannot be read or whose observation indices are out of
+ *     range; more than 1024 nodes or 8192 edges in a graph; more than 65536 nodes, 32768 edges, 131072 blocks of the
+ *     factors or 4194304 factor updates in a call (together these keep a call's device workspace under 256 MiB).
+ *     n == 0 returns SG_OK before the handle or the device is touched.  A failing call writes nothing.
+ * One graph occupies one workgroup, whatever its size: a 1000-node graph does not use more of the device than an
+ * 8-node one.  No communicator is involved: rank-local on a sharded handle.
+ * Not in scope: merging duplicated landmarks; information matrices beyond three weights; switchable constraints; any
+ * multi-workgroup solve of one graph. */
+enum sg_posegraph_status {
+  SG_PG_OK = 0,            /* the solve finished with ok = 1 */
+  SG_PG_DID_NOT_RUN = 1,   /* no free node, or no edge touches a free node (decided on the host) */
+  SG_PG_NO_ANCHOR = 2,     /* a connected component that holds a free node holds no fixed node (decided on the host) */
+  SG_PG_FAILED = 3         /* the solve ended with ok = 0 */
+};
+
+typedef struct sg_posegraph_options {
+  double range;          /* CauchyLoss range on |r|^2; 0: no loss */
+  int32_t fix_scale;     /* != 0: sigma = 0 everywhere, 6 unknowns per node */
+  int32_t move_points;   /* != 0: move the map's points with their anchor frames (host) */
+} sg_posegraph_options;
+
+void sg_posegraph_options_default(sg_posegraph_options* o);   /* range 0, fix_scale 0, move_points 0 */
+int sg_slam_optimize_pose_graph(sg_slam* s, sg_map* map, const int32_t* node_frame /*[N]*/,
+                                const int32_t* node_fixed /*[N]*/, const int32_t* node_offset /*[n+1]*/,
+                                const int32_t* edge_ab /*[2E]*/, const double* edge_meas /*[8E]*/,
+                                const double* edge_weight /*[3E]*/, const int32_t* edge_offset /*[n+1]*/, int32_t n,
+                                const sg_posegraph_options* options, int32_t* status /*[n]*/,
+                                double* log_scale /*[N], may be NULL*/, sg_solver_summary* summaries /*[n], may be NULL*/);
+
+/* The measurement of each listed frame pair (a, b) = pairs[2 i], pairs[2 i + 1] as the map stands: meas[8 i ..] =
+ * q^ (4), u^ (3), rho^ of sg_slam_optimize_pose_graph.  Host only: no handle, no device; the map is not written.
+ *   - sim == NULL: q^ = q_a (x) conj(q_b) (normalised, w >= 0), u^ = R_a (t_b - t_a), rho^ = 0: an odometry or
+ *     covisibility edge, with zero residual at entry.
+ *   - sim = scale, q[4], t[3] (8 doubles, exactly sg_align_result's Y = scale R(q) X + t from a's piece to b's): frame a
+ *     is first moved as sg_map_apply_similarity would move it and takes the local scale s:
+ *         t_a' = s R_S t_a + t_S,  q_a' = q_a (x) conj(q_S);
+ *         q^ = q_a' (x) conj(q_b),  u^ = R_a' (t_b - t_a') / s,  rho^ = -ln s.
+ *     This is the one place where an sg_slam_align_points result becomes a loop edge.
+ * SG_EINVAL, with nothing written: a null map, or a null pairs or meas with n > 0; n < 0; a frame index out of range;
+ * a == b; a map whose poses cannot be read; sim with the faults sg_map_apply_similarity refuses (scale <= 0 or not
+ * finite, q not unit to 1e-9, a non-finite t). */
+int sg_map_pose_edges(const sg_map* map, const int32_t* pairs /*[2n]*/, int32_t n, const double* sim /*[8] or NULL*/,
+                      double* meas /*[8n]*/);
+
+/* The pairs of listed frames that share at least min_shared slam-usable points through observations with
+ * obs_disabled == 0 (the point filter of sg_slam_solve_frame_poses): candidates for covisibility edges.  Host only.
+ * A pair is (i, j), i < j, positions in frames[]; pairs come in lexicographic order.  Two-call filling: *count is
+ * always the full number, and at most cap pairs (2 cap ints) are written to pairs_out (may be NULL with cap == 0).
+ * SG_EINVAL: a null map or count, a null frames with nf > 0, a null pairs_out with cap > 0; nf < 0, cap < 0,
+ * min_shared < 1; a frame index out of range or listed twice; a map whose observations cannot be read or whose
+ * observation indices are out of range. */
+int sg_map_covisible_pairs(const sg_map* map, const int32_t* frames /*[nf]*/, int32_t nf, int32_t min_shared,
+                           int32_t* pairs_out /*[2 cap]*/, int32_t cap, int32_t* count);
 
 /* ------------------------------------------------------------------------------------------------
  * Front end: HessianTracker (hessian.h:9-270) and the forward/backward matching step of Matcher

@@ -12,6 +12,7 @@
 #include "ba_align.h"
 #include "ba_points.h"
 #include "ba_pose.h"
+#include "ba_posegraph.h"
 #include "ba_relpose.h"
 #include "ba_solver.h"
 #include "comm.h"
@@ -33,6 +34,7 @@ struct sg_slam {
   std::unique_ptr<sg::PointSolver> points;   // created on first use (sg_slam_solve_points)
   std::unique_ptr<sg::RelPoseSolver> relpose;   // created on first use (sg_slam_relative_poses)
   std::unique_ptr<sg::AlignSolver> align;   // created on first use (sg_slam_align_points)
+  std::unique_ptr<sg::PoseGraphSolver> posegraph;   // created on first use (sg_slam_optimize_pose_graph)
   sg_device_options dev;
   sg_solver_options options;
   int32_t iterations = 0;    // Slam::iterations_ (slam.cpp:517)
@@ -496,6 +498,93 @@ int sg_slam_debug_align_kernel_ms(sg_slam* s, double* ms) {
   SG_CAPI_BEGIN
   SG_REQUIRE(s && ms, SG_EINVAL, "null argument");
   *ms = AlignSolverOf(s).last_kernel_ms();
+  SG_CAPI_END
+}
+
+static sg::PoseGraphSolver& PoseGraphSolverOf(sg_slam* s) {
+  if (!s->posegraph) s->posegraph.reset(new sg::PoseGraphSolver(s->dev, s->solver->stream()));   // one stream per Slam object
+  return *s->posegraph;
+}
+
+int sg_slam_optimize_pose_graph(sg_slam* s, sg_map* map, const int32_t* node_frame, const int32_t* node_fixed,
+                                const int32_t* node_offset, const int32_t* edge_ab, const double* edge_meas,
+                                const double* edge_weight, const int32_t* edge_offset, int32_t n,
+                                const sg_posegraph_options* options, int32_t* status, double* log_scale,
+                                sg_solver_summary* summaries) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s && map && options, SG_EINVAL, "null argument");
+  sg::PgPlan plan;
+  sg::PlanPoseGraph(map, node_frame, node_fixed, node_offset, edge_ab, edge_meas, edge_weight, edge_offset, n, options,
+                    &plan);   // every argument check, on the host
+  if (n == 0) return SG_OK;   // nothing to optimise: neither the handle nor the device is touched
+  SG_REQUIRE(status, SG_EINVAL, "null status array");
+  if (plan.num_run == 0) {   // every status was decided on the host: the device is not touched
+    for (int g = 0; g < n; ++g) status[g] = plan.graphs[g].status;
+    for (int i = 0; log_scale && i < node_offset[n]; ++i) log_scale[i] = 0.0;
+    sg_solver_summary none{};
+    none.termination_type = SG_DID_NOT_RUN;
+    for (int g = 0; summaries && g < n; ++g) summaries[g] = none;
+    return SG_OK;
+  }
+  sg::PoseGraphSolver& ps = PoseGraphSolverOf(s);
+  ps.Solve(map, plan, *options, s->options, status, log_scale, summaries);
+  // Slam::Run's bookkeeping (slam.cpp:517-518) over the graphs that ran, in list order
+  for (const sg_solver_summary& sum : ps.summaries()) {
+    if (sum.termination_type == SG_DID_NOT_RUN) continue;
+    s->iterations += sum.num_iterations;
+    s->error = sum.final_cost;
+    s->last = sum;
+  }
+  SG_CAPI_END
+}
+
+// Diagnostics (not in the public header): HIP-event time of the k_posegraph_lm launch, and the same call solved by
+// the planner's CPU executor on the host, no handle and no device (tools/posegraph_bench.py's baseline, and the
+// CPU tests' check of the plan and the arithmetic the kernel shares).
+int sg_slam_debug_posegraph_timing(sg_slam* s, int32_t enable) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s, SG_EINVAL, "null handle");
+  PoseGraphSolverOf(s).SetTiming(enable != 0);
+  SG_CAPI_END
+}
+
+int sg_slam_debug_posegraph_kernel_ms(sg_slam* s, double* ms) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s && ms, SG_EINVAL, "null argument");
+  *ms = PoseGraphSolverOf(s).last_kernel_ms();
+  SG_CAPI_END
+}
+
+int sg_posegraph_debug_cpu_solve(sg_map* map, const int32_t* node_frame, const int32_t* node_fixed,
+                                 const int32_t* node_offset, const int32_t* edge_ab, const double* edge_meas,
+                                 const double* edge_weight, const int32_t* edge_offset, int32_t n,
+                                 const sg_posegraph_options* options, const sg_solver_options* solver, int32_t* status,
+                                 double* log_scale, sg_solver_summary* summaries) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(map && options && solver, SG_EINVAL, "null argument");
+  sg::PgPlan plan;
+  sg::PlanPoseGraph(map, node_frame, node_fixed, node_offset, edge_ab, edge_meas, edge_weight, edge_offset, n, options,
+                    &plan);
+  if (n == 0) return SG_OK;
+  SG_REQUIRE(status, SG_EINVAL, "null status array");
+  std::vector<double> ws(plan.WorkspaceDoubles(), 0.0), xres(plan.x0);
+  const sg::PgView v = plan.View(ws.data());
+  sg_solver_summary none{};
+  none.termination_type = SG_DID_NOT_RUN;
+  std::vector<sg_solver_summary> sums((size_t)n, none);
+  for (int g = 0; g < n; ++g) {
+    const sg::PgGraph& G = plan.graphs[g];
+    status[g] = G.status;
+    if (!G.run) continue;
+    sg::PgOut out{};
+    sg::PgCpuSolve(v, G, *solver, &out);
+    sg::PgSummarize(out, &sums[g]);
+    if (!out.ok) status[g] = SG_PG_FAILED;
+    std::copy(v.x[out.cur] + sg::kPgState * (size_t)G.node0, v.x[out.cur] + sg::kPgState * (size_t)(G.node0 + G.nn),
+              xres.begin() + sg::kPgState * (size_t)G.node0);
+  }
+  sg::PgWriteBack(map, plan, status, xres.data(), options->move_points, log_scale);
+  for (int g = 0; summaries && g < n; ++g) summaries[g] = sums[g];
   SG_CAPI_END
 }
 

@@ -358,6 +358,127 @@ int sg_map_apply_similarity(sg_map* map, double scale, const double* q, const do
   SG_CAPI_END
 }
 
+void sg_posegraph_options_default(sg_posegraph_options* o) {
+  o->range = 0.0;          // no loss
+  o->fix_scale = 0;
+  o->move_points = 0;
+}
+
+int sg_map_pose_edges(const sg_map* map, const int32_t* pairs, int32_t n, const double* sim, double* meas) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(map, SG_EINVAL, "null map");
+  SG_REQUIRE(n >= 0, SG_EINVAL, "negative count");
+  SG_REQUIRE(n == 0 || (pairs && meas), SG_EINVAL, "null pair list or output");
+  SG_REQUIRE(map->num_frames >= 0, SG_EINVAL, "negative map sizes");
+  SG_REQUIRE(n == 0 || (map->q && map->t), SG_EINVAL, "the map's poses cannot be read");
+  double s = 1.0, qs[4] = {0.0, 0.0, 0.0, 1.0}, ts[3] = {0.0, 0.0, 0.0};
+  if (sim) {
+    s = sim[0];
+    SG_REQUIRE(std::isfinite(s) && s > 0.0, SG_EINVAL, "scale must be positive and finite");
+    const double n2 = (sim[1] * sim[1] + sim[2] * sim[2]) + (sim[3] * sim[3] + sim[4] * sim[4]);
+    SG_REQUIRE(std::fabs(n2 - 1.0) <= 1e-9, SG_EINVAL, "q is not a unit quaternion");   // (false for NaN)
+    SG_REQUIRE(std::isfinite(sim[5]) && std::isfinite(sim[6]) && std::isfinite(sim[7]), SG_EINVAL, "t is not finite");
+    const double in = 1.0 / std::sqrt(n2);
+    for (int k = 0; k < 4; ++k) qs[k] = sim[1 + k] * in;
+    for (int k = 0; k < 3; ++k) ts[k] = sim[5 + k];
+  }
+  for (int i = 0; i < n; ++i) {
+    const int a = pairs[2 * (size_t)i], b = pairs[2 * (size_t)i + 1];
+    SG_REQUIRE(a >= 0 && a < map->num_frames && b >= 0 && b < map->num_frames, SG_EINVAL, "frame index out of range");
+    SG_REQUIRE(a != b, SG_EINVAL, "a pair of one frame");
+  }
+  // Hamilton product on Eigen memory, and p = R(q) d by the standard matrix of a unit quaternion
+  const auto mul = [](const double* p, const double* c, double* r) {
+    r[0] = p[3] * c[0] + p[0] * c[3] + p[1] * c[2] - p[2] * c[1];
+    r[1] = p[3] * c[1] - p[0] * c[2] + p[1] * c[3] + p[2] * c[0];
+    r[2] = p[3] * c[2] + p[0] * c[1] - p[1] * c[0] + p[2] * c[3];
+    r[3] = p[3] * c[3] - p[0] * c[0] - p[1] * c[1] - p[2] * c[2];
+  };
+  const auto unit = [](double* q) {
+    double rn = 1.0 / std::sqrt((q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3]));
+    if (q[3] < 0.0) rn = -rn;
+    for (int k = 0; k < 4; ++k) q[k] *= rn;
+  };
+  const auto rot = [](const double* q, const double* d, double* p) {
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
+    p[0] = (1.0 - 2.0 * (y * y + z * z)) * d[0] + 2.0 * (x * y - w * z) * d[1] + 2.0 * (x * z + w * y) * d[2];
+    p[1] = 2.0 * (x * y + w * z) * d[0] + (1.0 - 2.0 * (x * x + z * z)) * d[1] + 2.0 * (y * z - w * x) * d[2];
+    p[2] = 2.0 * (x * z - w * y) * d[0] + 2.0 * (y * z + w * x) * d[1] + (1.0 - 2.0 * (x * x + y * y)) * d[2];
+  };
+  const double cs[4] = {-qs[0], -qs[1], -qs[2], qs[3]};
+  for (int i = 0; i < n; ++i) {
+    const int a = pairs[2 * (size_t)i], b = pairs[2 * (size_t)i + 1];
+    const double* qb = map->q + 4 * (size_t)b;
+    const double* tb = map->t + 3 * (size_t)b;
+    double qa[4], ta[3];
+    for (int k = 0; k < 4; ++k) qa[k] = map->q[4 * (size_t)a + k];
+    for (int k = 0; k < 3; ++k) ta[k] = map->t[3 * (size_t)a + k];
+    if (sim) {   // frame a as sg_map_apply_similarity would leave it
+      double r4[4], rt[3];
+      mul(qa, cs, r4);
+      unit(r4);
+      rot(qs, ta, rt);
+      for (int k = 0; k < 4; ++k) qa[k] = r4[k];
+      for (int k = 0; k < 3; ++k) ta[k] = s * rt[k] + ts[k];
+    }
+    double* o = meas + 8 * (size_t)i;
+    const double cb[4] = {-qb[0], -qb[1], -qb[2], qb[3]};
+    mul(qa, cb, o);
+    unit(o);
+    double qu[4] = {qa[0], qa[1], qa[2], qa[3]};
+    unit(qu);
+    const double d[3] = {tb[0] - ta[0], tb[1] - ta[1], tb[2] - ta[2]};
+    rot(qu, d, o + 4);
+    for (int k = 0; k < 3; ++k) o[4 + k] /= s;
+    o[7] = sim ? -std::log(s) : 0.0;
+  }
+  SG_CAPI_END
+}
+
+int sg_map_covisible_pairs(const sg_map* map, const int32_t* frames, int32_t nf, int32_t min_shared,
+                           int32_t* pairs_out, int32_t cap, int32_t* count) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(map && count, SG_EINVAL, "null argument");
+  SG_REQUIRE(nf >= 0 && cap >= 0 && min_shared >= 1, SG_EINVAL, "bad count");
+  SG_REQUIRE((nf == 0 || frames) && (cap == 0 || pairs_out), SG_EINVAL, "null list");
+  SG_REQUIRE(map->num_frames >= 0 && map->num_points >= 0 && map->num_obs >= 0, SG_EINVAL, "negative map sizes");
+  SG_REQUIRE(map->num_obs == 0 || (map->obs_frame && map->obs_point && map->obs_disabled && map->point_flags),
+             SG_EINVAL, "the map's observations cannot be read");
+  std::vector<int32_t> pos((size_t)map->num_frames, -1);
+  for (int i = 0; i < nf; ++i) {
+    SG_REQUIRE(frames[i] >= 0 && frames[i] < map->num_frames, SG_EINVAL, "frame index out of range");
+    SG_REQUIRE(pos[frames[i]] < 0, SG_EINVAL, "frame listed twice");
+    pos[frames[i]] = i;
+  }
+  // per point, the list positions that see it through an enabled observation (each once)
+  std::vector<std::vector<int32_t>> seen_by((size_t)map->num_points);
+  for (int o = 0; o < map->num_obs; ++o) {
+    const int f = map->obs_frame[o], p = map->obs_point[o];
+    SG_REQUIRE(f >= 0 && f < map->num_frames && p >= 0 && p < map->num_points, SG_EINVAL,
+               "observation index out of range");
+    if (map->obs_disabled[o] || pos[f] < 0 || (map->point_flags[p] & sg::kUnusableMask) != 0) continue;
+    std::vector<int32_t>& v = seen_by[p];
+    if (std::find(v.begin(), v.end(), pos[f]) == v.end()) v.push_back(pos[f]);
+  }
+  std::vector<int32_t> shared((size_t)nf * nf, 0);
+  for (const std::vector<int32_t>& v : seen_by)
+    for (size_t i = 0; i < v.size(); ++i)
+      for (size_t j = i + 1; j < v.size(); ++j)
+        shared[(size_t)std::min(v[i], v[j]) * nf + std::max(v[i], v[j])] += 1;
+  int32_t c = 0;
+  for (int i = 0; i < nf; ++i)
+    for (int j = i + 1; j < nf; ++j) {
+      if (shared[(size_t)i * nf + j] < min_shared) continue;
+      if (c < cap) {
+        pairs_out[2 * (size_t)c] = i;
+        pairs_out[2 * (size_t)c + 1] = j;
+      }
+      c += 1;
+    }
+  *count = c;
+  SG_CAPI_END
+}
+
 void sg_device_options_default(sg_device_options* o) {
   o->device = 0;
   o->precision = 0;

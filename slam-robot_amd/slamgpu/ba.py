@@ -409,6 +409,92 @@ class Slam:
                                                fr.ctypes.data_as(ip), len(fr), pt.ctypes.data_as(ip), len(pt)),
               "Slam::ApplySimilarity")
 
+    def PoseEdges(self, m: MapArrays, pairs, sim=None) -> np.ndarray:
+        """sg_map_pose_edges: the (n, 8) measurements q^ (4), u^ (3), rho^ of the listed frame pairs (a, b) as the map
+        stands (on the host; the map is not written).  sim = (scale, q, t), an AlignPoints result from a's piece to
+        b's, makes loop edges: frame a is taken as ApplySimilarity would leave it, at local scale `scale`."""
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        meas = np.zeros((len(pr), 8))
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        sm = None
+        if sim is not None:
+            sm = np.concatenate([[float(sim[0])], np.asarray(sim[1], dtype=np.float64).reshape(4),
+                                 np.asarray(sim[2], dtype=np.float64).reshape(3)])
+        ms = m.struct()
+        check(self.lib.sg_map_pose_edges(C.byref(ms), pr.ctypes.data_as(ip), len(pr),
+                                         sm.ctypes.data_as(dp) if sm is not None else None, meas.ctypes.data_as(dp)),
+              "Slam::PoseEdges")
+        return meas
+
+    def CovisiblePairs(self, m: MapArrays, frames, min_shared: int) -> np.ndarray:
+        """sg_map_covisible_pairs: the (K, 2) pairs (i < j, positions in `frames`, lexicographic) of listed frames that
+        share at least min_shared slam-usable points through enabled observations (on the host)."""
+        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        ip = C.POINTER(C.c_int32)
+        cnt = C.c_int32()
+        ms = m.struct()
+        check(self.lib.sg_map_covisible_pairs(C.byref(ms), fr.ctypes.data_as(ip), len(fr), int(min_shared), None, 0,
+                                              C.byref(cnt)), "Slam::CovisiblePairs")
+        out = np.zeros((max(cnt.value, 1), 2), dtype=np.int32)
+        check(self.lib.sg_map_covisible_pairs(C.byref(ms), fr.ctypes.data_as(ip), len(fr), int(min_shared),
+                                              out.ctypes.data_as(ip), cnt.value, C.byref(cnt)), "Slam::CovisiblePairs")
+        return out[:cnt.value]
+
+    def OptimizePoseGraph(self, m: MapArrays, graphs, range_: float = 0.0, fix_scale: bool = False,
+                          move_points: bool = False, cpu: bool = False, options=None) -> list:
+        """Pose-graph optimisation (sg_slam_optimize_pose_graph): spreads loop closures over the frames.  Each graph
+        is a dict with "frames" (map frame indices), "fixed" (one flag per node), "edges" ((E, 2) positions a, b in
+        the node list), "meas" ((E, 8): q^, u^, rho^ as PoseEdges gives them) and "weights" ((E, 3): w_rot, w_t,
+        w_s).  All graphs of a call run in one device launch, one workgroup each.  Updates m.q / m.t of the free nodes
+        of the solved graphs in place (and m.X with move_points).  Returns one dict per graph: "status" (a PG_STATUS
+        name), "log_scale" (one per node) and the fields of its solver summary.  cpu=True solves the same call with
+        the planner's CPU executor on the host instead (a development aid: no handle, no device; `options`, an
+        SgSolverOptions, defaults to default_solver_options())."""
+        from .capi import PG_STATUS, SgPosegraphOptions, default_solver_options
+        n = len(graphs)
+        noff = np.zeros(n + 1, dtype=np.int32)
+        eoff = np.zeros(n + 1, dtype=np.int32)
+        fr, fx, ab, meas, wts = [], [], [], [], []
+        for i, g in enumerate(graphs):
+            fr.append(np.asarray(g["frames"], dtype=np.int32).reshape(-1))
+            fx.append(np.asarray(g["fixed"], dtype=np.int32).reshape(-1))
+            ab.append(np.asarray(g["edges"], dtype=np.int32).reshape(-1, 2))
+            meas.append(np.asarray(g["meas"], dtype=np.float64).reshape(-1, 8))
+            wts.append(np.asarray(g["weights"], dtype=np.float64).reshape(-1, 3))
+            if not (len(fr[i]) == len(fx[i]) and len(ab[i]) == len(meas[i]) == len(wts[i])):
+                raise ValueError("graph %d: list lengths differ" % i)
+            noff[i + 1] = noff[i] + len(fr[i])
+            eoff[i + 1] = eoff[i] + len(ab[i])
+        cat = lambda v, dt, w: (np.ascontiguousarray(np.concatenate(v), dtype=dt) if n else np.zeros((0, w), dtype=dt))
+        fr_, fx_ = cat(fr, np.int32, 1).reshape(-1), cat(fx, np.int32, 1).reshape(-1)
+        ab_, meas_, wts_ = cat(ab, np.int32, 2), cat(meas, np.float64, 8), cat(wts, np.float64, 3)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        ls = np.zeros(max(int(noff[n]), 1))
+        sums = (SgSolverSummary * max(n, 1))()
+        opt = SgPosegraphOptions(range=range_, fix_scale=int(bool(fix_scale)), move_points=int(bool(move_points)))
+        ms = m.struct()
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        lists = (fr_.ctypes.data_as(ip), fx_.ctypes.data_as(ip), noff.ctypes.data_as(ip), ab_.ctypes.data_as(ip),
+                 meas_.ctypes.data_as(dp), wts_.ctypes.data_as(dp), eoff.ctypes.data_as(ip), n, C.byref(opt))
+        if cpu:
+            so = options if options is not None else default_solver_options()
+            fn = self.lib.sg_posegraph_debug_cpu_solve
+            fn.restype = C.c_int
+            fn.argtypes = [C.POINTER(type(ms)), ip, ip, ip, ip, dp, dp, ip, C.c_int32, C.POINTER(SgPosegraphOptions),
+                           C.POINTER(type(so)), ip, dp, C.POINTER(SgSolverSummary)]
+            check(fn(C.byref(ms), *lists, C.byref(so), status.ctypes.data_as(ip), ls.ctypes.data_as(dp), sums),
+                  "sg_posegraph_debug_cpu_solve")
+        else:
+            check(self.lib.sg_slam_optimize_pose_graph(self.h, C.byref(ms), *lists, status.ctypes.data_as(ip),
+                                                       ls.ctypes.data_as(dp), sums), "Slam::OptimizePoseGraph")
+        out = []
+        for i in range(n):
+            d = sums[i].as_dict()
+            d["status"] = PG_STATUS.get(int(status[i]), "?")
+            d["log_scale"] = ls[noff[i]:noff[i + 1]].copy()
+            out.append(d)
+        return out
+
     def SolvePoints(self, m: MapArrays, points, range_: float) -> list:
         """Structure-only bundle adjustment (sg_slam_solve_points): each listed point's location against the map's
         frames as they are, all points in one device launch.  Point flags are not consulted.  Updates m.X of the

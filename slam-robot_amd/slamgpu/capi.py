@@ -165,6 +165,13 @@ class SgAlignResult(C.Structure):
         return d
 
 
+PG_STATUS = {0: "OK", 1: "DID_NOT_RUN", 2: "NO_ANCHOR", 3: "FAILED"}
+
+
+class SgPosegraphOptions(C.Structure):
+    _fields_ = [("range", C.c_double), ("fix_scale", C.c_int32), ("move_points", C.c_int32)]
+
+
 class SgBaInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("num_frames", "num_points", "num_obs", "num_blocks", "n", "band_tiles",
                                          "cholesky_path", "num_pairs", "rank", "nranks", "cholesky_split",
@@ -417,6 +424,11 @@ SYMBOLS = {
     "sg_slam_align_points": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, _ip, C.c_int32, C.POINTER(SgAlignOptions),
                                        _ip, C.POINTER(SgAlignResult), _ip]),
     "sg_map_apply_similarity": (C.c_int, [C.POINTER(SgMap), C.c_double, _dp, _dp, _ip, C.c_int32, _ip, C.c_int32]),
+    "sg_posegraph_options_default": (None, [C.POINTER(SgPosegraphOptions)]),
+    "sg_slam_optimize_pose_graph": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, _ip, _ip, _ip, _dp, _dp, _ip, C.c_int32,
+                                              C.POINTER(SgPosegraphOptions), _ip, _dp, C.POINTER(SgSolverSummary)]),
+    "sg_map_pose_edges": (C.c_int, [C.POINTER(SgMap), _ip, C.c_int32, _dp, _dp]),
+    "sg_map_covisible_pairs": (C.c_int, [C.POINTER(SgMap), _ip, C.c_int32, C.c_int32, _ip, C.c_int32, _ip]),
     "sg_triangulate_options_default": (None, [C.POINTER(SgTriangulateOptions)]),
     "sg_slam_triangulate_points": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32,
                                              C.POINTER(SgTriangulateOptions), _ip, C.POINTER(SgTriangulateResult),
