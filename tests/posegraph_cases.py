@@ -29,7 +29,30 @@ OPTIONS = dict(max_num_iterations=1000, function_tolerance=1e-7, gradient_tolera
 # rounding floor: ring8 runs until the step itself vanishes.
 SCENE_OPTIONS = {"ring8": dict(parameter_tolerance=1e-12, gradient_tolerance=1e-18)}
 
-SCENES = ("ring8", "drift12", "chords24", "rigid12", "badloop12", "long300")
+SCENES = ("ring8", "drift12", "chords24", "rigid12", "badloop12", "long300",
+          "far12", "farrigid12", "farcauchy12", "complete48", "star40")
+
+# Scenes that do not end converged, each with the options that take it there.  They stay out of SCENES: their result
+# is a status, a termination type and the four step counts (and for maxiter the states after two steps), not a minimum.
+#   loose9, loose9_3   ring8's ring and a node 8 that hangs on one edge (3, 8) of weight LOOSE_W; with min_lm_diagonal = 0
+#                      the node's damped block is exactly 0, every step meets a pivot that is exactly 0 (invalid) and the
+#                      solve ends NUMERICAL_FAILURE after max_num_consecutive_invalid_steps of them (5, and 3).  The
+#                      planner's ties go to the lower list position, so node 8 is the last column, a column without rows;
+#   loose_first9       the same with the loose node at list position 1 (on the edge (4, 1)): the first column;
+#   loose_last9        the loose node joined to every ring node: the last column, below a block in every other column;
+#   maxiter_chords24   chords24 stopped by max_num_iterations = 2: NO_CONVERGENCE;
+#   minradius_far12    far12 with min_trust_region_radius = 2000: the first steps are rejected and the radius test ends it.
+PATH_SCENES = ("loose9", "loose9_3", "loose_first9", "loose_last9", "maxiter_chords24", "minradius_far12")
+LOOSE_NODE = {"loose9": 8, "loose9_3": 8, "loose_first9": 1, "loose_last9": 8}
+LOOSE_W = 1e-200                        # J is of order 1e-197: J^T J and J^T r underflow to exactly 0
+SCENE_OPTIONS.update({
+    "loose9": dict(min_lm_diagonal=0.0),
+    "loose9_3": dict(min_lm_diagonal=0.0, max_num_consecutive_invalid_steps=3),
+    "loose_first9": dict(min_lm_diagonal=0.0),
+    "loose_last9": dict(min_lm_diagonal=0.0),
+    "maxiter_chords24": dict(max_num_iterations=2),
+    "minradius_far12": dict(min_trust_region_radius=2000.0),
+})
 
 # The reference's own rounding floor per scene: the worst difference between the reference solved with the nodes and
 # edges in listed order and in reversed order, in rotation (deg), centre (map units), log-scale and final cost.
@@ -43,6 +66,12 @@ SPREAD = {
     "rigid12": {"rot_deg": 3.7e-14, "t": 4.1e-13, "log_scale": 0.0, "cost": 1.4e-12},
     "badloop12": {"rot_deg": 3.6e-14, "t": 6.1e-13, "log_scale": 3.5e-16, "cost": 8.2e-12},
     "long300": {"rot_deg": 3.9e-14, "t": 2.5e-12, "log_scale": 4.3e-16, "cost": 5.7e-18},
+    "far12": {"rot_deg": 5.6e-14, "t": 1.6e-12, "log_scale": 7.6e-16, "cost": 2.1e-16},
+    "farrigid12": {"rot_deg": 6.9e-14, "t": 1.6e-12, "log_scale": 0.0, "cost": 2.8e-18},
+    "farcauchy12": {"rot_deg": 2.5e-14, "t": 1.1e-12, "log_scale": 2.3e-15, "cost": 0.0},
+    "complete48": {"rot_deg": 2.4e-14, "t": 4.5e-13, "log_scale": 1.8e-15, "cost": 2.8e-14},
+    "star40": {"rot_deg": 3.7e-14, "t": 6.8e-13, "log_scale": 1.4e-19, "cost": 1.0e-18},
+    "maxiter_chords24": {"rot_deg": 2.9e-14, "t": 4.5e-13, "log_scale": 6.6e-16, "cost": 4.6e-16},
 }
 
 _cache = {}
@@ -191,7 +220,8 @@ def evaluate(sc, x, jac=True):
 
 def solve_np(sc, options=None):
     """The Ceres 1.8 LM on the scene, dense.  Returns a dict: x (N, 8), the summary fields, rho1 per edge at the
-    result and `trace`, per iteration the termination quantities as (value, threshold) pairs."""
+    result and `trace`, per iteration the termination quantities as (value, threshold) pairs, and under "decision" the
+    step's relative decrease with min_relative_decrease."""
     o = dict(OPTIONS)
     o.update(options or {})
     fs = sc["fix_scale"]
@@ -272,6 +302,7 @@ def solve_np(sc, options=None):
                 res["termination"] = "FUNCTION_TOLERANCE"
                 break
             rel = change / model
+            tq["decision"] = (rel, o["min_relative_decrease"])
             accepted = rel > o["min_relative_decrease"]
         if accepted:
             res["num_successful_steps"] += 1
@@ -338,6 +369,89 @@ def reference(name):
     return _cache[("ref", name)]
 
 
+def reversed_reference(name):
+    """The reference on the scene listed backwards (its x is in reversed node order)."""
+    if ("rev", name) not in _cache:
+        _cache[("rev", name)] = solve_np(reversed_scene(scene(name)), SCENE_OPTIONS.get(name))
+    return _cache[("rev", name)]
+
+
+def entry_matrix(sc, options=None):
+    """The first step's dense matrix S J^T J S + D / radius at the entry state, as solve_np builds it, and the free
+    nodes in its block order."""
+    o = dict(OPTIONS)
+    o.update(options or {})
+    D = 6 if sc["fix_scale"] else 7
+    free = [i for i in range(len(sc["q"])) if not sc["fixed"][i]]
+    col = {nd: j for j, nd in enumerate(free)}
+    x = np.zeros((len(sc["q"]), 8))
+    x[:, :4], x[:, 4:7] = sc["q"], sc["t"]
+    _, J, _, _, _ = evaluate(sc, x)
+    A = np.zeros((7 * len(sc["edges"]), D * len(free)))
+    for i, (a, b) in enumerate(sc["edges"]):
+        if a in col:
+            A[7 * i:7 * i + 7, D * col[a]:D * col[a] + D] = J[i][:, 0:D]
+        if b in col:
+            A[7 * i:7 * i + 7, D * col[b]:D * col[b] + D] = J[i][:, 7:7 + D]
+    As = A * (1.0 / (1.0 + np.sqrt((A * A).sum(0))) if o["jacobi_scaling"] else 1.0)
+    diag = np.clip((As * As).sum(0), o["min_lm_diagonal"], o["max_lm_diagonal"])
+    return As.T @ As + np.diag(diag / o["initial_trust_region_radius"]), free
+
+
+def column_rows(sc):
+    """The planner's elimination order restated (csrc/posegraph_plan.cpp: greedy minimum degree on the block graph of
+    the free nodes with an exact fill simulation, ties to the lower list position): per column in elimination order
+    (node, number of off-diagonal blocks of L below its diagonal block)."""
+    free = [i for i in range(len(sc["q"])) if not sc["fixed"][i]]
+    adj = {i: set() for i in free}
+    for a, b in sc["edges"]:
+        if a in adj and b in adj:
+            adj[int(a)].add(int(b))
+            adj[int(b)].add(int(a))
+    out = []
+    while adj:
+        v = min(adj, key=lambda i: (len(adj[i]), i))
+        nb = adj.pop(v)
+        out.append((v, len(nb)))
+        for p in nb:
+            adj[p].discard(v)
+            adj[p] |= nb - {p}
+    return out
+
+
+def compute_cap1024():
+    """cap1024 by the reference, listed and reversed: what tests/golden/posegraph_cap1024.npz holds.  Dense, 7161
+    unknowns: minutes, and about 6 GB."""
+    sc = scene("cap1024")
+    ref = solve_np(sc)
+    rev = solve_np(reversed_scene(sc))
+    spread = compare(ref["x"], rev["x"][::-1])
+    spread["cost"] = abs(ref["final_cost"] - rev["final_cost"])
+    out = {k: ref[k] for k in ("num_iterations", "num_successful_steps", "num_unsuccessful_steps", "num_invalid_steps",
+                               "ok", "termination", "initial_cost", "final_cost", "x", "trace")}
+    out.update(x_reversed=rev["x"][::-1].copy(), spread=spread,
+               reversed_counts={k: rev[k] for k in ("num_iterations", "num_successful_steps", "num_unsuccessful_steps",
+                                                    "num_invalid_steps", "ok", "termination")})
+    return out
+
+
+def golden_cap1024():
+    """The committed reference result of cap1024 (tests/golden/make_posegraph_golden.py; the dense solve takes
+    minutes): x and x_reversed (N, 8, the latter in listed node order), the summary fields and `spread`, the listed
+    against reversed differences."""
+    if "golden_cap1024" not in _cache:
+        import os
+        with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "posegraph_cap1024.npz")) as z:
+            g = {k: z[k] for k in z.files}
+        out = {k: int(g[k]) for k in ("num_iterations", "num_successful_steps", "num_unsuccessful_steps",
+                                      "num_invalid_steps", "ok")}
+        out.update(x=g["x"], x_reversed=g["x_reversed"], termination=str(g["termination"]),
+                   initial_cost=float(g["initial_cost"]), final_cost=float(g["final_cost"]),
+                   spread={k: float(g["spread_" + k]) for k in ("rot_deg", "t", "log_scale", "cost")})
+        _cache["golden_cap1024"] = out
+    return _cache["golden_cap1024"]
+
+
 def solver_options(name):
     """The scene's sg_solver_options (slamgpu.capi.SgSolverOptions)."""
     from slamgpu.capi import default_solver_options
@@ -351,6 +465,81 @@ def states(m, frames, log_scale):
     x[:, 4:7] = m.t.reshape(-1, 3)[frames]
     x[:, 7] = log_scale
     return x
+
+
+def check_cap1024(x, out):
+    """cap1024's result (x (1024, 8) states, out the graph's result) against the committed reference result: counts and
+    termination equal, states within MARGIN times the golden's own listed-against-reversed spread, the final cost
+    within MARGIN * max(that spread, cost_floor), and the error against the truth by ring8's rule."""
+    g, sc = golden_cap1024(), scene("cap1024")
+    keys = ("num_iterations", "num_successful_steps", "num_unsuccessful_steps", "num_invalid_steps")
+    print("cap1024", {k: out[k] for k in ("status", "termination") + keys + ("final_cost",)},
+          "the reference:", {k: g[k] for k in ("termination",) + keys + ("final_cost",)})
+    assert out["status"] == "OK" and out["ok"] == 1 and out["termination"] == g["termination"]
+    for key in keys:
+        assert out[key] == g[key], (key, out[key], g[key])
+    assert abs(out["initial_cost"] - g["initial_cost"]) <= 1e-12 * g["initial_cost"]
+    d = compare(x, g["x"])
+    d["cost"] = abs(out["final_cost"] - g["final_cost"])
+    bounds = {k: MARGIN * g["spread"][k] for k in d}
+    bounds["cost"] = MARGIN * max(g["spread"]["cost"], cost_floor(sc))
+    print("cap1024 against the reference:", d, "bounds:", bounds)
+    for key, val in d.items():
+        assert val <= bounds[key], (key, val, bounds[key])
+    xt = np.zeros_like(x)
+    xt[:, :4], xt[:, 4:7] = sc["q_true"], sc["t_true"]
+    own, got = compare(g["x"], xt), compare(x, xt)
+    print("cap1024 against the truth:", got, "the reference:", own)
+    for key in got:
+        assert got[key] <= MARGIN * max(own[key], g["spread"][key]), key
+    assert (x[0, :4] == sc["q"][0]).all() and (x[0, 4:7] == sc["t"][0]).all() and x[0, 7] == 0.0
+    assert (np.abs(np.linalg.norm(x[1:, :4], axis=1) - 1.0) <= 4e-16).all() and (x[1:, 3] >= 0).all()
+
+
+def written_back_q(q, fixed):
+    """What the write-back of an SG_PG_OK graph leaves of the quaternions q (N, 4) when no step was accepted
+    (include/slamgpu.h: "q_f normalised with w >= 0 ... of its free nodes"; csrc/posegraph_plan.cpp, PgWriteBack): the
+    normalisation moves a unit quaternion by an ulp here and there, and it is applied whether or not the node moved."""
+    q = np.array(q, float)
+    rn = 1.0 / np.sqrt((q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + (q[:, 2] * q[:, 2] + q[:, 3] * q[:, 3]))
+    rn = np.where(q[:, 3] < 0.0, -rn, rn)
+    return np.where(np.asarray(fixed, bool)[:, None], q, q * rn[:, None])
+
+
+def check_path_result(name, out, m, before):
+    """What the CPU executor and the device are both held to on a scene of PATH_SCENES solved alone on a map of its
+    frames: `out` the graph's result, `m` the map after the call, `before` a copy from before it.
+
+    A FAILED graph's frames are untouched bit for bit.  minradius_far12 ends OK without an accepted step, and an OK
+    graph is written back: its t is the entry's bit for bit, its q the entry's as the write-back normalises it, bit
+    for bit (on the CPU executor 16 of the 48 components differ from the entry's, by 2.2e-16 at most, so "equal to
+    the entry bit for bit" is not what the documented write-back gives)."""
+    sc, ref = scene(name), reference(name)
+    print(name, {k: out[k] for k in ("status", "termination", "ok", "num_iterations", "num_successful_steps",
+                                     "num_unsuccessful_steps", "num_invalid_steps", "initial_cost", "final_cost")})
+    print(name, "the reference:", {k: ref[k] for k in ("termination", "ok", "num_iterations", "num_successful_steps",
+                                                       "num_unsuccessful_steps", "num_invalid_steps", "initial_cost")})
+    assert out["status"] == ("OK" if ref["ok"] else "FAILED") and out["ok"] == ref["ok"]
+    assert out["termination"] == ref["termination"]
+    for key in ("num_iterations", "num_successful_steps", "num_unsuccessful_steps", "num_invalid_steps"):
+        assert out[key] == ref[key], (key, out[key], ref[key])
+    assert abs(out["initial_cost"] - ref["initial_cost"]) <= 1e-12 * ref["initial_cost"]
+    if name == "maxiter_chords24":
+        d = compare(states(m, np.arange(len(sc["q"])), out["log_scale"]), ref["x"])
+        d["cost"] = abs(out["final_cost"] - ref["final_cost"])
+        print(name, "against the reference after two steps:", d, "bounds:", {k: bound(name, k) for k in d})
+        for key, val in d.items():
+            assert val <= bound(name, key), (key, val, bound(name, key))
+    else:
+        # no step was accepted (FAILED, or the radius test after rejected steps): nothing moved, bit for bit
+        assert ref["num_successful_steps"] == 0
+        want_q = before.q if not ref["ok"] else written_back_q(before.q.reshape(-1, 4), sc["fixed"]).reshape(-1)
+        print(name, "q components that differ from the entry's:", int((m.q != before.q).sum()), "by at most",
+              float(np.abs(m.q - before.q).max()))
+        assert m.q.tobytes() == want_q.tobytes() and m.t.tobytes() == before.t.tobytes()
+        assert np.abs(m.q - before.q).max() <= 2.0 * EPS
+        assert (out["log_scale"] == 0.0).all()
+        assert abs(out["final_cost"] - ref["initial_cost"]) <= 1e-12 * ref["initial_cost"]
 
 
 # ---------------------------------------------------------------------------------------------- measurements
@@ -493,6 +682,39 @@ def scene(name):
         ed = [(i, i + k) for i in range(N) for k in (1, 2, 3) if i + k < N]
         ed += [(299, 0), (250, 40), (200, 75), (150, 10), (280, 120)]
         sc = _exact(name, N, ed, [0], 300, radius=4000.0, rot_deg=1.0, trans=10.0)
+    elif name == "far12":
+        # a start far outside the basin (120 degrees, 1500 map units on a circle of radius 1000): LM rejects steps
+        sc = _exact(name, 12, [(i, (i + 1) % 12) for i in range(12)], [0], 112, rot_deg=120.0, trans=1500.0)
+    elif name == "farrigid12":
+        # the same with fix_scale, on a seed of its own: far12's start ends within a factor 2 of the gradient
+        # tolerance when the scale is fixed, which the reference-bounds test does not allow
+        sc = _exact(name, 12, [(i, (i + 1) % 12) for i in range(12)], [0], 137, rot_deg=120.0, trans=1500.0)
+        sc["fix_scale"] = True
+    elif name == "farcauchy12":
+        sc = dict(scene("far12"), name=name, range=BAD_RANGE)
+    elif name == "minradius_far12":
+        sc = dict(scene("far12"), name=name)
+    elif name == "maxiter_chords24":
+        sc = dict(scene("chords24"), name=name)
+    elif name == "complete48":
+        # every pair an edge: the column eliminated j-th has 46 - j off-diagonal blocks, so the first ten columns
+        # give the strided loops over rows * D items (up to 322) a second trip
+        sc = _exact(name, 48, [(a, b) for a in range(48) for b in range(a + 1, 48)], [0], 148)
+    elif name == "star40":
+        # a free hub of 39 edges, a leaf fixed: one block and one gradient segment gather 39 contributions
+        sc = _exact(name, 40, [(0, b) for b in range(1, 40)], [1], 141)
+    elif name in LOOSE_NODE:
+        members = [0, 2, 3, 4, 5, 6, 7, 8] if name == "loose_first9" else list(range(8))
+        ring = [(members[i], members[(i + 1) % 8]) for i in range(8)]
+        loose = {"loose_first9": [(4, 1)], "loose_last9": [(i, 8) for i in range(8)]}.get(name, [(3, 8)])
+        sc = _exact(name, 9, ring + loose, [0], 109)
+        sc["weights"][len(ring):] = LOOSE_W
+    elif name == "cap1024":
+        # the node cap (kPgMaxNodes): long300's construction, edges to the next 3 nodes and five long chords
+        N = 1024
+        ed = [(i, i + k) for i in range(N) for k in (1, 2, 3) if i + k < N]
+        ed += [(1023, 0), (850, 140), (700, 260), (500, 30), (960, 410)]
+        sc = _exact(name, N, ed, [0], 1029, radius=12000.0, rot_deg=1.0, trans=10.0)
     elif name == "two_comp":
         a = _exact("a", 6, [(i, (i + 1) % 6) for i in range(6)], [0], 61)
         b = _exact("b", 5, [(i, (i + 1) % 5) for i in range(5)], [], 62)

@@ -2,7 +2,8 @@
 around it (sg_map_pose_edges, sg_map_covisible_pairs, the move_points step): needs the library but no GPU.  Every
 argument error is found by the host-only planner before the device is touched, so an opaque dummy handle is enough.
 The planner's CPU executor (sg_posegraph_debug_cpu_solve, the same plan and arithmetic the kernel follows) is held to
-the numpy reference on every scene here, so that a fault of the plan or the arithmetic shows without a device."""
+the numpy reference on every scene here, the scenes that end failed, unconverged or by the radius test (PATH_SCENES)
+and the graph at the node cap included, so that a fault of the plan or the arithmetic shows without a device."""
 import ctypes as C
 
 import numpy as np
@@ -267,6 +268,33 @@ def test_cpu_executor_solves_every_scene_as_the_reference_does(name):
         assert val <= pc.bound(name, key), (key, val, pc.bound(name, key))
     fixed = np.flatnonzero(sc["fixed"])
     assert (m.q.reshape(-1, 4)[fixed] == sc["q"][fixed]).all() and (m.t.reshape(-1, 3)[fixed] == sc["t"][fixed]).all()
+    if name == "complete48":
+        # the scene is there for the strided loops' second trip: column j of a complete graph's 47 has 46 - j rows
+        rows = [r for _, r in pc.column_rows(sc)]
+        assert rows == list(range(46, -1, -1)) and sum(7 * r > 256 for r in rows) == 10
+
+
+@pytest.mark.parametrize("name", pc.PATH_SCENES)
+def test_cpu_executor_takes_the_paths_that_do_not_end_converged(name):
+    s = pc.host_slam()
+    sc = pc.scene(name)
+    m = pc.frames_map(sc["q"], sc["t"])
+    before = m.copy()
+    out = s.OptimizePoseGraph(m, [pc.graph_of(sc)], range_=sc["range"], fix_scale=sc["fix_scale"], cpu=True,
+                              options=pc.solver_options(name))[0]
+    pc.check_path_result(name, out, m, before)
+
+
+def test_cpu_executor_solves_cap1024_behind_another_graph():
+    """A graph at the node cap behind complete48 in one call (large node0, col0 and block offsets), against the
+    committed reference result: the plan and the index arithmetic the kernel shares, without a device."""
+    s = pc.host_slam()
+    scs = [pc.scene("complete48"), pc.scene("cap1024")]
+    m = pc.frames_map(np.vstack([sc["q"] for sc in scs]), np.vstack([sc["t"] for sc in scs]))
+    graphs = [pc.graph_of(scs[0], np.arange(48)), pc.graph_of(scs[1], 48 + np.arange(1024))]
+    out = s.OptimizePoseGraph(m, graphs, cpu=True)
+    assert out[0]["status"] == "OK" and out[0]["num_iterations"] == pc.reference("complete48")["num_iterations"]
+    pc.check_cap1024(pc.states(m, 48 + np.arange(1024), out[1]["log_scale"]), out[1])
 
 
 def _drifted_c1():

@@ -2,7 +2,10 @@
 status, termination type and iteration counts equal the reference's, its final cost, poses and log-scales within
 MARGIN * SPREAD (the reference's own rounding floor, recomputed by tests/test_posegraph_reference_bounds.py);
 reproducibility bit for bit, alone and beside other graphs in either order; a graph without an anchor beside a solved
-one; and the loop-closing chain AlignPoints -> PoseEdges(sim) -> OptimizePoseGraph(move_points)."""
+one; the paths off the converging one (rejected steps, invalid steps up to SG_PG_FAILED, NO_CONVERGENCE, the radius
+test; PATH_SCENES and the far scenes), alone and beside solved graphs in one launch; a graph at the node cap behind
+another one, against the committed reference result; and the loop-closing chain AlignPoints -> PoseEdges(sim) ->
+OptimizePoseGraph(move_points)."""
 import numpy as np
 import pytest
 
@@ -33,6 +36,8 @@ def test_scene_matches_the_reference(name):
     m, (x,), (out,), slam = _solve([name])
     print(name, {k: out[k] for k in ("status", "termination", "num_iterations", "num_successful_steps",
                                      "num_unsuccessful_steps", "num_invalid_steps", "final_cost")})
+    print(name, "the reference:", {k: ref[k] for k in ("termination", "num_iterations", "num_successful_steps",
+                                                       "num_unsuccessful_steps", "num_invalid_steps", "final_cost")})
     d = pc.compare(x, ref["x"])
     d["cost"] = abs(out["final_cost"] - ref["final_cost"])
     print(name, "against the reference:", d, "bounds:", {k: pc.bound(name, k) for k in d})
@@ -56,8 +61,10 @@ def test_scene_matches_the_reference(name):
         for key in got:   # MARGIN times the reference's own error against the truth, never below its rounding floor
             assert got[key] <= pc.MARGIN * max(own[key], pc.SPREAD[name][key]), key
         assert out["final_cost"] < 1e-20
-    if name == "rigid12":
+    if name in ("rigid12", "farrigid12"):
         assert (out["log_scale"] == 0.0).all()
+    if name in ("far12", "farrigid12", "farcauchy12"):   # rejected steps: the solve goes on from the kept state
+        assert out["num_unsuccessful_steps"] >= (1 if name == "farcauchy12" else 3)
     if name == "drift12":
         assert np.ptp(out["log_scale"][1:]) > 0.05 and out["log_scale"][0] == 0.0
 
@@ -97,6 +104,88 @@ def test_a_graph_without_an_anchor_beside_a_solved_one():
     _, (alone,), _, _ = _solve(["ring8"])
     assert xb.tobytes() == alone.tobytes() and not (xb[1:, 4:7] == ring["t"][1:]).any()
     assert slam.iterations() == out[1]["num_iterations"]
+
+
+COUNTS = ("num_iterations", "num_successful_steps", "num_unsuccessful_steps", "num_invalid_steps")
+
+
+@pytest.mark.parametrize("name", pc.PATH_SCENES)
+def test_paths_that_do_not_end_converged(name):
+    """Invalid steps up to NUMERICAL_FAILURE (the pivot that is exactly 0 in the first, a middle and the last column),
+    NO_CONVERGENCE at max_num_iterations, and rejected steps down to min_trust_region_radius: status, termination and
+    all four counts equal the reference's, and the map is left as the contract says."""
+    sc, ref = pc.scene(name), pc.reference(name)
+    slam = Slam(options=pc.solver_options(name))
+    prev = None
+    for _ in range(2):   # the second call reuses the handle's workspace after a failed graph
+        m = pc.frames_map(sc["q"], sc["t"])
+        before, it0 = m.copy(), slam.iterations()
+        out = slam.OptimizePoseGraph(m, [pc.graph_of(sc)], range_=sc["range"], fix_scale=sc["fix_scale"])[0]
+        pc.check_path_result(name, out, m, before)
+        assert slam.iterations() - it0 == ref["num_iterations"]
+        last = slam.last_summary()
+        print(name, "sg_slam_last_summary:", {k: last[k] for k in ("ok", "termination") + COUNTS})
+        assert last["ok"] == ref["ok"] and last["termination"] == ref["termination"]
+        for key in COUNTS:
+            assert last[key] == ref[key], key
+        if prev is not None:
+            assert out["final_cost"] == prev[0]["final_cost"]
+            assert out["trust_region_radius"] == prev[0]["trust_region_radius"]
+            assert m.q.tobytes() == prev[1].q.tobytes() and m.t.tobytes() == prev[1].t.tobytes()
+        prev = (out, m)
+
+
+def test_failed_and_rejecting_graphs_beside_solved_ones():
+    """One launch holds graphs that reject steps, fail on invalid steps, have no anchor and solve at once, in both
+    orders: each workgroup's control flow is its own.  Every graph runs with min_lm_diagonal = 0, which the loose
+    scenes need and which changes nothing for the others (tests/test_posegraph_reference_bounds.py)."""
+    from slamgpu.capi import default_solver_options
+    names = ["far12", "loose9", "two_comp", "complete48", "loose_last9", "ring8"]
+    want = dict(zip(names, ["OK", "FAILED", "NO_ANCHOR", "OK", "FAILED", "OK"]))
+    opt = lambda: default_solver_options(min_lm_diagonal=0.0)
+    alone = {}
+    for n in names:
+        if want[n] == "OK":
+            _, (x,), (o,), _ = _solve([n], slam=Slam(options=opt()))
+            alone[n] = (x, o)
+    far, ref = alone["far12"][1], pc.reference("far12")
+    print("far12 alone with min_lm_diagonal = 0:", {k: far[k] for k in COUNTS}, "the reference:", {k: ref[k] for k in COUNTS})
+    assert far["num_unsuccessful_steps"] >= 3 and all(far[k] == ref[k] for k in COUNTS)
+    slam = Slam(options=opt())
+    for order in (names, names[::-1]):
+        it0 = slam.iterations()
+        _, xs, out, _ = _solve(order, slam=slam)
+        print([(n, o["status"], o["termination"], o["num_iterations"], o["num_unsuccessful_steps"], o["num_invalid_steps"])
+               for n, o in zip(order, out)])
+        assert [o["status"] for o in out] == [want[n] for n in order]
+        for n, x, o in zip(order, xs, out):
+            sc = pc.scene(n)
+            if want[n] == "OK":
+                x1, o1 = alone[n]
+                assert x.tobytes() == x1.tobytes(), n
+                for key in ("final_cost", "initial_cost", "trust_region_radius", "termination") + COUNTS:
+                    assert o[key] == o1[key], (n, key)
+            else:
+                assert (x[:, :4] == sc["q"]).all() and (x[:, 4:7] == sc["t"]).all() and (x[:, 7] == 0).all(), n
+            if want[n] == "FAILED":
+                assert o["ok"] == 0 and o["termination"] == "NUMERICAL_FAILURE"
+                assert (o["num_invalid_steps"], o["num_unsuccessful_steps"], o["num_successful_steps"]) == (5, 4, 0)
+            if want[n] == "NO_ANCHOR":
+                assert o["termination"] == "DID_NOT_RUN" and o["num_iterations"] == 0
+        # the facade counts the graphs that ran, failed ones included, and keeps the last of them
+        assert slam.iterations() - it0 == sum(o["num_iterations"] for o in out)
+        last = [o for o in out if o["termination"] != "DID_NOT_RUN"][-1]
+        assert slam.last_summary()["num_iterations"] == last["num_iterations"] and slam.error() == last["final_cost"]
+
+
+def test_cap1024_behind_another_graph():
+    """A graph at the node cap (kPgMaxNodes) in the second place of a call, behind complete48: node0 = 48, col0 = 47,
+    1128 edges and 1128 blocks of L ahead of its own."""
+    _, (xc, x), (oc, out), _ = _solve(["complete48", "cap1024"])
+    assert oc["status"] == "OK" and oc["num_iterations"] == pc.reference("complete48")["num_iterations"]
+    d = pc.compare(xc, pc.reference("complete48")["x"])
+    assert all(d[k] <= pc.bound("complete48", k) for k in d), d
+    pc.check_cap1024(x, out)
 
 
 def test_loop_closing_chain_beats_one_rigid_similarity():
