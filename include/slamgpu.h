@@ -682,6 +682,66 @@ int sg_slam_align_points(sg_slam* s, sg_map* map, const int32_t* corr /*[2M]: po
 int sg_map_apply_similarity(sg_map* map, double scale, const double* q /*[4]*/, const double* t /*[3]*/,
                             const int32_t* frames /*[nf]*/, int32_t nf, const int32_t* points /*[np]*/, int32_t np);
 
+/* Match by projection: given a pose, which landmarks does this frame see?  sg_hamming_match compares every keypoint
+ * with every descriptor of the map and ignores geometry; once sg_slam_localize_frames, sg_slam_optimize_pose_graph or
+ * plain tracking has given a frame a pose, this call recovers the frame's other keypoints by a guided search: the
+ * listed points are projected into each listed frame, and a keypoint's 256-bit descriptor (4 x u64, the convention
+ * of sg_hamming_match) is compared only with the points that project inside a pixel window around it.  All frames of
+ * a call run in three launches.  K = kp_offset[n]; the keypoints of the i-th listed frame f = frames[i] are
+ * kp_offset[i] .. kp_offset[i + 1], pixels kp_xy[2 k], kp_xy[2 k + 1].
+ *   1. Candidates of frame f: position j of points[] is a candidate when Project(q_f, t_f, k[frame_camera[f]],
+ *      X[points[j]]) of csrc/project_math.h, in fp64, accepts it (not behind the camera: p.z >= 0.001 W), the projected
+ *      u and v are finite, the projection lies in [0, width) x [0, height) when a bound is given (width = height = 0:
+ *      no bound), and, with skip_observed, frame f has no observation of that point with obs_disabled == 0.  Point
+ *      flags are not consulted (the convention of sg_slam_solve_points).  num_projected counts them.
+ *   2. Window of keypoint k of frame f: the candidates with (u - x)^2 + (v - y)^2 <= radius_px^2, each product and
+ *      the sum rounded once, in fp64.  A keypoint with a non-finite pixel has an empty window.
+ *      num_candidates[k] is the window's size; best_point[k] the map index of the candidate with the smallest
+ *      (popcount(kp XOR point), position j), or -1 for an empty window; best_dist[k] that popcount, or -1;
+ *      second_dist[k] the second smallest distance of the window as a multiset (sg_hamming_match's rule: equal to
+ *      best_dist on a tie), or -1 with fewer than two candidates.
+ *   3. match[k], decided on the host from those arrays: keypoint k is accepted when best_point >= 0, best_dist <=
+ *      max_dist and either second_dist < 0 or 100 best_dist <= ratio_percent second_dist (integers).  Within one listed
+ *      frame, a point claimed by several accepted keypoints goes to the one with the smallest (best_dist, keypoint
+ *      index); the other claimants get -1 (no fall-back to their second choice).  match[k] is a map point index or -1.
+ *   4. results[i] (may be NULL): the frame's keypoints, its candidates, its keypoints with a non-empty window and its
+ *      matches.  best_point, best_dist, second_dist and num_candidates may be NULL too.
+ *   - A frame may be listed more than once, each time with its own keypoints.  A frame's results do not depend on its
+ *     position in the call and are reproducible bit for bit.  With K == 0 or np == 0 nothing is launched and the
+ *     outputs are the empty answers (-1, -1, -1, -1, 0; num_projected 0 too).  The map is never written; sg_slam_iterations, sg_slam_error
+ *     and sg_slam_last_summary do not move.  No communicator is involved: rank-local on a sharded handle.
+ *   - SG_EINVAL, all found on the host before the device is touched, with nothing written: a null s, map, options or
+ *     match; n < 0 or np < 0; with n > 0 a null frames or kp_offset, a null kp_xy or kp_desc when K > 0, a null points
+ *     or point_desc when np > 0; kp_offset[0] != 0 or a decreasing offset; a frame or point index out of range; a point
+ *     listed twice; radius_px not above 0 or not finite; width or height negative, or only one of them zero; max_dist
+ *     outside 0..256; ratio_percent outside 1..100; K > 2^20; n np > 2^22 (the index bits of the packed key, and a
+ *     workspace near 200 MiB: split the frames over calls); a map whose poses, cameras or (np > 0) points cannot be
+ *     read, a frame whose camera index is out of range; with skip_observed, a map whose observations cannot be read or
+ *     whose observation indices are out of range.  n == 0 returns SG_OK before the handle or the device is touched.
+ * Not in scope: scale or octave prediction and viewing-angle tests; a per-point radius; writing observations into the
+ * map; a spatial grid. */
+typedef struct sg_match_options {
+  double radius_px;        /* > 0 and finite */
+  int32_t width, height;   /* both > 0: a projection outside [0, width) x [0, height) is no candidate; both 0: no bound */
+  int32_t max_dist;        /* 0..256 */
+  int32_t ratio_percent;   /* 1..100 */
+  int32_t skip_observed;   /* != 0: a point the frame already observes (obs_disabled == 0) is no candidate for it */
+} sg_match_options;
+
+typedef struct sg_match_result {
+  int32_t num_keypoints, num_projected, num_with_candidates, num_matched;
+} sg_match_result;
+
+void sg_match_options_default(sg_match_options* o);   /* 12.0, 0, 0, 64, 80, 1 */
+int sg_slam_match_by_projection(sg_slam* s, const sg_map* map, const int32_t* frames /*[n]*/, int32_t n,
+                                const int32_t* kp_offset /*[n+1]*/, const double* kp_xy /*[2K]*/,
+                                const uint64_t* kp_desc /*[4K]*/, const int32_t* points /*[np]*/, int32_t np,
+                                const uint64_t* point_desc /*[4 np]*/, const sg_match_options* options,
+                                int32_t* match /*[K]*/, int32_t* best_point /*[K], may be NULL*/,
+                                int32_t* best_dist /*[K], may be NULL*/, int32_t* second_dist /*[K], may be NULL*/,
+                                int32_t* num_candidates /*[K], may be NULL*/,
+                                sg_match_result* results /*[n], may be NULL*/);
+
 /* Pose-graph optimisation: spread a loop closure over the frames.  sg_slam_align_points gives the similarity that
  * joins two pieces of a map, and sg_map_apply_similarity moves one piece rigidly; but the drift of a long run is not a
  * rigid offset of one piece.  This call distributes it over the trajectory, scale included, so that the window solve

@@ -10,6 +10,7 @@
 #include <memory>
 
 #include "ba_align.h"
+#include "ba_match.h"
 #include "ba_points.h"
 #include "ba_pose.h"
 #include "ba_posegraph.h"
@@ -35,6 +36,7 @@ struct sg_slam {
   std::unique_ptr<sg::RelPoseSolver> relpose;   // created on first use (sg_slam_relative_poses)
   std::unique_ptr<sg::AlignSolver> align;   // created on first use (sg_slam_align_points)
   std::unique_ptr<sg::PoseGraphSolver> posegraph;   // created on first use (sg_slam_optimize_pose_graph)
+  std::unique_ptr<sg::MatchSolver> match;   // created on first use (sg_slam_match_by_projection)
   sg_device_options dev;
   sg_solver_options options;
   int32_t iterations = 0;    // Slam::iterations_ (slam.cpp:517)
@@ -498,6 +500,60 @@ int sg_slam_debug_align_kernel_ms(sg_slam* s, double* ms) {
   SG_CAPI_BEGIN
   SG_REQUIRE(s && ms, SG_EINVAL, "null argument");
   *ms = AlignSolverOf(s).last_kernel_ms();
+  SG_CAPI_END
+}
+
+static sg::MatchSolver& MatchSolverOf(sg_slam* s) {
+  if (!s->match) s->match.reset(new sg::MatchSolver(s->dev, s->solver->stream()));   // one stream per Slam object
+  return *s->match;
+}
+
+int sg_slam_match_by_projection(sg_slam* s, const sg_map* map, const int32_t* frames, int32_t n,
+                                const int32_t* kp_offset, const double* kp_xy, const uint64_t* kp_desc,
+                                const int32_t* points, int32_t np, const uint64_t* point_desc,
+                                const sg_match_options* options, int32_t* match, int32_t* best_point,
+                                int32_t* best_dist, int32_t* second_dist, int32_t* num_candidates,
+                                sg_match_result* results) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s && map && options && match, SG_EINVAL, "null argument");
+  sg::MatchPlan plan;
+  sg::PlanMatch(map, frames, n, kp_offset, kp_xy, kp_desc, points, np, point_desc, options,
+                &plan);   // every argument check, on the host
+  if (n == 0) return SG_OK;   // nothing to match: neither the handle nor the device is touched
+  const size_t K = (size_t)plan.K;
+  // the empty answers; with K == 0 or np == 0 they stand, and the device is not touched
+  std::vector<int32_t> bp(K, -1), bd(K, -1), sd(K, -1), nc(K, 0), proj((size_t)n, 0), mt(K, -1);
+  if (plan.launch)
+    MatchSolverOf(s).Run(plan, kp_xy, kp_desc, points, point_desc, *options, bp.data(), bd.data(), sd.data(), nc.data(),
+                         proj.data());
+  std::vector<sg_match_result> res((size_t)n, sg_match_result{});
+  for (int i = 0; i < n; ++i) {
+    res[i].num_keypoints = kp_offset[i + 1] - kp_offset[i];
+    res[i].num_projected = proj[i];
+  }
+  sg::ResolveMatches(kp_offset, n, bp.data(), bd.data(), sd.data(), nc.data(), *options, mt.data(), res.data());
+  std::copy(mt.begin(), mt.end(), match);
+  if (best_point) std::copy(bp.begin(), bp.end(), best_point);
+  if (best_dist) std::copy(bd.begin(), bd.end(), best_dist);
+  if (second_dist) std::copy(sd.begin(), sd.end(), second_dist);
+  if (num_candidates) std::copy(nc.begin(), nc.end(), num_candidates);
+  if (results) std::copy(res.begin(), res.end(), results);
+  SG_CAPI_END
+}
+
+// Diagnostics (not in the public header): HIP-event time of sg_slam_match_by_projection's three launches
+// (tools/match_bench.py).
+int sg_slam_debug_match_timing(sg_slam* s, int32_t enable) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s, SG_EINVAL, "null handle");
+  MatchSolverOf(s).SetTiming(enable != 0);
+  SG_CAPI_END
+}
+
+int sg_slam_debug_match_kernel_ms(sg_slam* s, double* ms) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s && ms, SG_EINVAL, "null argument");
+  *ms = MatchSolverOf(s).last_kernel_ms();
   SG_CAPI_END
 }
 

@@ -304,6 +304,15 @@ void sg_align_options_default(sg_align_options* o) {
   o->min_gap = 1e-6;
 }
 
+void sg_match_options_default(sg_match_options* o) {
+  o->radius_px = 12.0;
+  o->width = 0;   // no image bound
+  o->height = 0;
+  o->max_dist = 64;
+  o->ratio_percent = 80;
+  o->skip_observed = 1;
+}
+
 int sg_map_apply_similarity(sg_map* map, double scale, const double* q, const double* t, const int32_t* frames,
                             int32_t nf, const int32_t* points, int32_t np) {
   SG_CAPI_BEGIN

@@ -396,6 +396,61 @@ class Slam:
             out.append(d)
         return out
 
+    def MatchByProjection(self, m: MapArrays, frames, keypoints, points, point_desc, radius_px: float = 12.0,
+                          max_dist: int = 64, ratio_percent: int = 80, skip_observed: bool = True, width: int = 0,
+                          height: int = 0) -> list:
+        """Match by projection (sg_slam_match_by_projection): which of the listed map points does each listed frame
+        see at its pose in m?  keypoints holds one (pixels (k, 2) float64, descriptors (k, 4) uint64) pair per listed
+        frame; point_desc the (len(points), 4) uint64 descriptors of the listed points.  The points are projected into
+        each frame on the device and a keypoint is compared only with the points inside radius_px of it; the accepted,
+        unique matches (max_dist, the ratio test at ratio_percent) come back as one int32 array per frame: a map point
+        index or -1 per keypoint.  With skip_observed, a point the frame already observes is no candidate; width and
+        height, when given, cull projections outside the image.  The map is not written.
+        projection_match_results() has the detail arrays and the per-frame counts."""
+        from .capi import SgMatchOptions, SgMatchResult
+        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        n = len(fr)
+        if len(keypoints) != n:
+            raise ValueError("one (pixels, descriptors) pair per listed frame")
+        xys = [np.ascontiguousarray(k[0], dtype=np.float64).reshape(-1, 2) for k in keypoints]
+        dss = [np.ascontiguousarray(k[1], dtype=np.uint64).reshape(-1, 4) for k in keypoints]
+        if any(len(a) != len(b) for a, b in zip(xys, dss)):
+            raise ValueError("one descriptor per keypoint")
+        off = np.zeros(n + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(a) for a in xys])
+        K = int(off[n])
+        xy = np.concatenate(xys).reshape(-1) if K else np.zeros(0)
+        ds = np.concatenate(dss).reshape(-1) if K else np.zeros(0, dtype=np.uint64)
+        pts = np.ascontiguousarray(points, dtype=np.int32).reshape(-1)
+        pd = np.ascontiguousarray(point_desc, dtype=np.uint64).reshape(-1)
+        if len(pd) != 4 * len(pts):
+            raise ValueError("one descriptor per listed point")
+        out = [np.full(max(K, 1), 7, dtype=np.int32) for _ in range(5)]
+        res = (SgMatchResult * max(n, 1))()
+        opt = SgMatchOptions(radius_px=radius_px, width=width, height=height, max_dist=max_dist,
+                             ratio_percent=ratio_percent, skip_observed=int(bool(skip_observed)))
+        ms = m.struct()
+        ip, dp, up = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+        # (empty arrays are passed by address: only the counts decide whether they are read)
+        check(self.lib.sg_slam_match_by_projection(
+            self.h, C.byref(ms), fr.ctypes.data_as(ip), n, off.ctypes.data_as(ip), xy.ctypes.data_as(dp),
+            ds.ctypes.data_as(up), pts.ctypes.data_as(ip), len(pts), pd.ctypes.data_as(up), C.byref(opt),
+            *[a.ctypes.data_as(ip) for a in out], res), "Slam::MatchByProjection")
+        names = ("match", "best_point", "best_dist", "second_dist", "num_candidates")
+        self._match_results = []
+        for i in range(n):
+            d = res[i].as_dict()
+            for name, a in zip(names, out):
+                d[name] = a[off[i]:off[i + 1]].copy()
+            self._match_results.append(d)
+        return [d["match"].copy() for d in self._match_results]
+
+    def projection_match_results(self) -> list:
+        """Result dicts of the last MatchByProjection call, one per listed frame: num_keypoints, num_projected,
+        num_with_candidates, num_matched and the per-keypoint int32 arrays match, best_point, best_dist, second_dist
+        and num_candidates."""
+        return list(getattr(self, "_match_results", []))
+
     def ApplySimilarity(self, m: MapArrays, scale: float, q, t, frames, points) -> None:
         """sg_map_apply_similarity: moves the listed frames and points of m through Y = scale R(q) X + t in place (on
         the host; pixels of moved frames on moved points do not change)."""

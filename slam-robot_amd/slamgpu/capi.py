@@ -26,6 +26,7 @@ BAD_LOCATION, NO_BASELINE, NO_OBSERVATIONS, MISMATCHED, BAD_FEATURE = range(5)
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _u8p = C.POINTER(C.c_uint8)
+_u64p = C.POINTER(C.c_uint64)
 
 
 class SgMap(C.Structure):
@@ -163,6 +164,19 @@ class SgAlignResult(C.Structure):
         d["best_sample"] = tuple(self.best_sample[:])
         d["q"], d["t"] = np.array(self.q[:]), np.array(self.t[:])
         return d
+
+
+class SgMatchOptions(C.Structure):
+    _fields_ = [("radius_px", C.c_double), ("width", C.c_int32), ("height", C.c_int32), ("max_dist", C.c_int32),
+                ("ratio_percent", C.c_int32), ("skip_observed", C.c_int32)]
+
+
+class SgMatchResult(C.Structure):
+    _fields_ = [("num_keypoints", C.c_int32), ("num_projected", C.c_int32), ("num_with_candidates", C.c_int32),
+                ("num_matched", C.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 PG_STATUS = {0: "OK", 1: "DID_NOT_RUN", 2: "NO_ANCHOR", 3: "FAILED"}
@@ -424,6 +438,10 @@ SYMBOLS = {
     "sg_slam_align_points": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, _ip, C.c_int32, C.POINTER(SgAlignOptions),
                                        _ip, C.POINTER(SgAlignResult), _ip]),
     "sg_map_apply_similarity": (C.c_int, [C.POINTER(SgMap), C.c_double, _dp, _dp, _ip, C.c_int32, _ip, C.c_int32]),
+    "sg_match_options_default": (None, [C.POINTER(SgMatchOptions)]),
+    "sg_slam_match_by_projection": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32, _ip, _dp, _u64p, _ip,
+                                              C.c_int32, _u64p, C.POINTER(SgMatchOptions), _ip, _ip, _ip, _ip, _ip,
+                                              C.POINTER(SgMatchResult)]),
     "sg_posegraph_options_default": (None, [C.POINTER(SgPosegraphOptions)]),
     "sg_slam_optimize_pose_graph": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, _ip, _ip, _ip, _dp, _dp, _ip, C.c_int32,
                                               C.POINTER(SgPosegraphOptions), _ip, _dp, C.POINTER(SgSolverSummary)]),
