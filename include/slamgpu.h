@@ -867,7 +867,10 @@ void sg_tracker_options_default(sg_tracker_options* o);
 int sg_tracker_create(sg_tracker** out, const sg_tracker_options* o, const sg_device_options* dev);
 void sg_tracker_destroy(sg_tracker* t);
 
-/* MakePyramid (hessian.h:95-126) of one image into pyramid slot `slot`. */
+/* MakePyramid (hessian.h:95-126) of one image into pyramid slot `slot`.  `stride` is bytes per row (cv::Mat's
+ * step), stride >= 3 * width (SG_EINVAL otherwise).  Bytes past 3 * width in a row are never read: the image may be
+ * a view into a wider one whose last row ends at the end of its allocation (stride * (height - 1) + 3 * width
+ * readable bytes suffice).  sg_frontend_track's image follows the same rule. */
 int sg_tracker_set_image(sg_tracker* t, int32_t slot, const uint8_t* bgr, int32_t width, int32_t height,
                          int32_t stride);
 /* Download pyramid level `level` of slot `slot` (width*height floats). */

@@ -81,7 +81,8 @@ def unproject(q, t, plane, distance):                            # localmap.cpp:
 
 
 class OracleMatcher:
-    def __init__(self):
+    def __init__(self, window=WINDOW):
+        self.window = window      # sg_tracker_options.window of the device matcher under test (kWindowSize: 13)
         self.features = {}        # point id -> {"point": idx, "matches": [(view_seq, x, y)]}
         self.views = []           # [{"seq", "frame", "pyr", "dims", "w", "h"}]
         self.next_fid = 0
@@ -93,7 +94,7 @@ class OracleMatcher:
 
     def _track(self, from_view, from_pt, to_view, levels, to_pt):
         """TrackFeature (matcher.cpp:173-206) + the retry of FindMatches (247-251)."""
-        out, acc, _ = oracle.track_fb(from_view["pyr"], to_view["pyr"], from_view["dims"], WINDOW,
+        out, acc, _ = oracle.track_fb(from_view["pyr"], to_view["pyr"], from_view["dims"], self.window,
                                       np.float32([from_pt]), np.float32([to_pt]), np.int32([levels]))
         return bool(acc[0]), (out[0, 0], out[0, 1])
 

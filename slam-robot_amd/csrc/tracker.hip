@@ -1419,8 +1419,14 @@ void Tracker::SetImage(int slot, const uint8_t* bgr, int w, int h, int stride) {
   s.pyr.Resize(total);
   tmp_.Resize((size_t)w * h);
   tmp2_.Resize((size_t)w * h);
-  img_.Resize((size_t)stride * h);
-  SG_HIP_CHECK(hipMemcpyAsync(img_.ptr, bgr, (size_t)stride * h, hipMemcpyHostToDevice, stream_));
+  // The device copy is packed (3 * w bytes per row): bytes past 3 * w in a row are not read, so an image that is a
+  // view into a wider one may end with its last pixel (stride * (h - 1) + 3 * w readable bytes).
+  const int row = 3 * w;
+  img_.Resize((size_t)row * h);
+  if (stride == row)
+    SG_HIP_CHECK(hipMemcpyAsync(img_.ptr, bgr, (size_t)row * h, hipMemcpyHostToDevice, stream_));
+  else
+    SG_HIP_CHECK(hipMemcpy2DAsync(img_.ptr, row, bgr, stride, row, h, hipMemcpyHostToDevice, stream_));
   // hessian.h:95-126: blur 1.1 at level 0, pyrDown + blur 0.8 per level; klt.h:100-130: no blur at level 0,
   // pyrDown + blur 0.6; brute.h:60-80: no blur at all
   const int mode = opt_.mode;
@@ -1428,11 +1434,11 @@ void Tracker::SetImage(int slot, const uint8_t* bgr, int w, int h, int stride) {
   SG_HIP_CHECK(hipEventRecord(ev_[2], stream_));
   const int bx = 256;
   if (mode == SG_TRACKER_HESSIAN) {
-    hipLaunchKernelGGL(k_gray_blur_row, dim3((w + bx - 1) / bx, h), dim3(bx), 0, stream_, img_.ptr, w, h, stride, b0,
+    hipLaunchKernelGGL(k_gray_blur_row, dim3((w + bx - 1) / bx, h), dim3(bx), 0, stream_, img_.ptr, w, h, row, b0,
                        tmp_.ptr);
     hipLaunchKernelGGL(k_blur_col, dim3((w + bx - 1) / bx, h), dim3(bx), 0, stream_, tmp_.ptr, w, h, b0, s.pyr.ptr);
   } else {
-    hipLaunchKernelGGL(k_gray_scale, dim3((w + bx - 1) / bx, h), dim3(bx), 0, stream_, img_.ptr, w, h, stride,
+    hipLaunchKernelGGL(k_gray_scale, dim3((w + bx - 1) / bx, h), dim3(bx), 0, stream_, img_.ptr, w, h, row,
                        s.pyr.ptr);
   }
   for (int l = 1; l < opt_.depth; ++l) {
@@ -1448,7 +1454,7 @@ void Tracker::SetImage(int slot, const uint8_t* bgr, int w, int h, int stride) {
   }
   SG_HIP_CHECK(hipEventRecord(ev_[3], stream_));
   s.grey.Resize((size_t)w * h);
-  hipLaunchKernelGGL(k_grey_u8, dim3((w + bx - 1) / bx, h), dim3(bx), 0, stream_, img_.ptr, w, h, stride, s.grey.ptr);
+  hipLaunchKernelGGL(k_grey_u8, dim3((w + bx - 1) / bx, h), dim3(bx), 0, stream_, img_.ptr, w, h, row, s.grey.ptr);
   SG_HIP_CHECK(hipGetLastError());
   // level table for the tracking kernel: {image, width, height} per level (scalar-loaded on the device)
   std::vector<uint8_t> tab(sizeof(LevelDev) * opt_.depth);

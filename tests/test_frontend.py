@@ -20,27 +20,7 @@ import oracle_matcher as om  # noqa: E402
 
 from slamgpu.video import SEQ_K as K, matcher_sequence as make_sequence  # noqa: E402
 from slamgpu.video import sequence_mark as _mark, sequence_pose as _pose, sequence_true_t as _true_t  # noqa: E402
-
-
-def run_oracle(frames):
-    omap = om.OracleMap(K, [], [], [])
-    mt = om.OracleMatcher()
-    log = []
-    for i, img in enumerate(frames):
-        q, t = _pose(i)
-        omap.q.append(list(q))
-        omap.t.append(list(t))
-        omap.frame_camera.append(0)
-        omap.obs[i] = []
-        omap.keyframe.append(0)
-        _mark(i, omap.flags, omap.uncertainty, len(omap.X))
-
-        def upd(i=i):   # Matcher::Track's update_frames: correct the new frame's pose, report it updated
-            omap.t[i] = list(_true_t(i))
-            return i % 2 == 1
-        assert mt.Track(img, i, omap, upd)
-        log.append(dict(mt.last_stats))
-    return omap, mt, log
+from tracker_cases import run_oracle  # noqa: E402  (shared with test_tracker_windows_gpu.py)
 
 
 @pytest.fixture(scope="module")
