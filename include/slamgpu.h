@@ -909,6 +909,31 @@ int sg_tracker_seed_features(sg_tracker* t, int32_t slot, const float* match_xy,
  * tracking kernels and of the pyramid kernels of the last sg_tracker_set_image. */
 int sg_tracker_kernel_ms(sg_tracker* t, double* track_ms, double* pyramid_ms);
 
+/* Describe keypoints: oriented 256-bit descriptors (a steered BRIEF of this project's own pattern,
+ * csrc/brief_pattern.h) read from the blurred float pyramid of slot `slot`, as the 4 x uint64 rows that
+ * sg_hamming_match and sg_slam_match_by_projection consume.  One device launch per call, keypoints on any levels.
+ * For keypoint i on level l = levels[i] (NULL = all 0) of size w_l x h_l:
+ *   centre  px = x 2^-l, py = y 2^-l in fp32 (exact); cx = (int)floorf(px + 0.5f), cy likewise.  SG_DESC_BORDER when
+ *           x or y is not finite, or cx < 15, cx > w_l - 16, cy < 15 or cy > h_l - 16 (a level narrower or lower
+ *           than 31 refuses every keypoint); a refused keypoint gets four zero words and angle_bin -1.
+ *   moments m10 = sum u I(cx + u, cy + v), m01 = sum v I(cx + u, cy + v) over the 709 pixels u^2 + v^2 <= 15^2, in
+ *           fp64 (every product is exact), in a fixed order without atomics: the same bits on every run and
+ *           wherever the keypoint stands in the call.
+ *   bin     angle_bin = 0 when m10 == 0 && m01 == 0, else the k in 0..31 whose direction 2 pi k / 32 is nearest
+ *           to atan2(m01, m10), image y pointing down (csrc/describe_math.h: the argmax over k of
+ *           fma(m10, cos_k, m01 * sin_k) on a constant table, ties to the lower k).
+ *   bits    bit j & 63 of word j >> 6 is I(cx + ax, cy + ay) < I(cx + bx, cy + by) on the float pixels for row
+ *           (ax, ay, bx, by) = pattern[k][j]; false on a tie.
+ * SG_EINVAL, found on the host before the device is touched and with nothing written: a null handle, n < 0,
+ * n > 2^20, null xy or desc with n > 0, a slot out of range or never set, a level outside 0..depth-1.  n == 0 returns
+ * SG_OK and launches nothing. */
+enum sg_describe_status { SG_DESC_OK = 0, SG_DESC_BORDER = 1 };
+int sg_tracker_describe(sg_tracker* t, int32_t slot, int32_t n, const float* xy /*[2n], level-0 pixels*/,
+                        const int32_t* levels /*[n], NULL = all 0*/, uint64_t* desc /*[4n]*/,
+                        int32_t* angle_bin /*[n], may be NULL*/, int32_t* status /*[n], may be NULL*/);
+/* HIP events around the last describe launch of this tracker. */
+int sg_tracker_describe_ms(sg_tracker* t, double* kernel_ms);
+
 /* ------------------------------------------------------------------------------------------------
  * All-pairs 256-bit descriptor matching (the matcher's brute-force descriptor distance; BASELINE config 4).
  * Descriptors are 4 x uint64 per row.  Per query row: best_idx = argmin over train rows of
@@ -989,6 +1014,11 @@ int sg_frontend_track(sg_frontend* f, const uint8_t* bgr, int32_t width, int32_t
                       sg_frontend_stats* stats);
 /* Live features: point handles and TrackedPoint ids in set order (ids ascending); n in/out = capacity/count. */
 int sg_frontend_features(sg_frontend* f, int32_t* points, int32_t* ids, int32_t* n);
+/* sg_tracker_describe on the pyramid of the keyframe view the front end holds for `frame` (a frame that became a
+ * keyframe and has not expired: at most the last four); SG_EINVAL when no view of that frame is held.  It reads
+ * the view only: sg_frontend_track behaves as if the call had not been made. */
+int sg_frontend_describe(sg_frontend* f, int32_t frame, int32_t n, const float* xy, const int32_t* levels,
+                         uint64_t* desc, int32_t* angle_bin, int32_t* status);
 
 #ifdef __cplusplus
 }

@@ -197,6 +197,17 @@ class Frontend {
     return 1;
   }
 
+  // sg_tracker_describe on the pyramid of the keyframe view held for `frame` (the newest, should a frame index
+  // have been tracked twice).  Reads the view's slot only: features, views and the free list are untouched.
+  void Describe(int frame, int n, const float* xy, const int32_t* levels, uint64_t* desc, int32_t* angle_bin,
+                int32_t* status) {
+    const View* view = nullptr;
+    for (auto& v : views_)
+      if (v.frame == frame) view = &v;
+    SG_REQUIRE(view, SG_EINVAL, "no keyframe view of that frame is held");
+    trk_->Describe(view->slot, n, xy, levels, desc, angle_bin, status);
+  }
+
   int Features(int32_t* points, int32_t* ids, int cap) const {
     int i = 0;
     for (auto& f : features_) {
@@ -358,6 +369,14 @@ int sg_frontend_features(sg_frontend* f, int32_t* points, int32_t* ids, int32_t*
   SG_CAPI_BEGIN
   SG_REQUIRE(f && n, SG_EINVAL, "null argument");
   *n = f->f->Features(points, ids, *n);
+  SG_CAPI_END
+}
+
+int sg_frontend_describe(sg_frontend* f, int32_t frame, int32_t n, const float* xy, const int32_t* levels,
+                         uint64_t* desc, int32_t* angle_bin, int32_t* status) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(f, SG_EINVAL, "null handle");
+  f->f->Describe(frame, n, xy, levels, desc, angle_bin, status);
   SG_CAPI_END
 }
 

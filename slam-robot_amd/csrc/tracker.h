@@ -47,6 +47,10 @@ class Tracker {
   // Matcher::Track's new-keyframe seeding (goodFeaturesToTrack + AddNewFeatures, corners.hip).
   void SeedFeatures(int slot, const float* match_xy, int nmatch, int max_corners, double quality, double min_distance,
                     float* corners_xy, int* ncorners, float* added_xy, int* nadded);
+  // sg_tracker_describe (describe.hip): oriented 256-bit descriptors of n keypoints on the levels of `slot`.
+  void Describe(int slot, int n, const float* xy, const int32_t* levels, uint64_t* desc, int32_t* angle_bin,
+                int32_t* status);
+  double describe_ms() const { return describe_ms_; }
   double track_ms() const { return track_ms_; }
   // diagnostics: accumulated per-phase cycles of k_track_fb since the last call (SG_TRK_STAMP=1), kTrkStamps
   std::vector<unsigned long long> Stamps();
@@ -64,7 +68,7 @@ class Tracker {
   sg_tracker_options opt_;
   sg_device_options dev_;
   hipStream_t stream_ = nullptr;
-  hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // track, pyramid, describe pairs
   std::vector<Slot> slots_;
   DBuf<float> mask_, tmp_, tmp2_;
   DBuf<uint8_t> img_;
@@ -85,6 +89,10 @@ class Tracker {
   bool stamp_on_ = false;
   DBuf<unsigned long long> stamps_;
   double track_ms_ = 0.0, pyr_ms_ = 0.0;
+  DBuf<float> desc_xy_;             // Describe's own buffers: a describe call leaves a loaded tracking batch alone
+  DBuf<int32_t> desc_lv_, desc_bin_, desc_st_;
+  DBuf<uint64_t> desc_out_;
+  double describe_ms_ = 0.0;
 };
 
 }  // namespace sg

@@ -136,4 +136,19 @@ int sg_tracker_track_feature(sg_tracker* t, int32_t from, int32_t to, int32_t n,
   SG_CAPI_END
 }
 
+int sg_tracker_describe(sg_tracker* t, int32_t slot, int32_t n, const float* xy, const int32_t* levels, uint64_t* desc,
+                        int32_t* angle_bin, int32_t* status) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(t, SG_EINVAL, "null handle");
+  t->t->Describe(slot, n, xy, levels, desc, angle_bin, status);
+  SG_CAPI_END
+}
+
+int sg_tracker_describe_ms(sg_tracker* t, double* kernel_ms) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(t && kernel_ms, SG_EINVAL, "null argument");
+  *kernel_ms = t->t->describe_ms();
+  SG_CAPI_END
+}
+
 }  // extern "C"

@@ -401,6 +401,8 @@ SYMBOLS = {
     "sg_tracker_track_feature": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _ip, _ip, _ip]),
     "sg_tracker_seed_features": (C.c_int, [C.c_void_p, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                            _fp, _ip, _fp, _ip]),
+    "sg_tracker_describe": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _fp, _ip, _u64p, _ip, _ip]),
+    "sg_tracker_describe_ms": (C.c_int, [C.c_void_p, _dp]),
     "sg_matcher_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SgDeviceOptions)]),
     "sg_matcher_destroy": (None, [C.c_void_p]),
     "sg_hamming_match": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_uint64), C.c_int32,
@@ -456,6 +458,7 @@ SYMBOLS = {
     "sg_frontend_track": (C.c_int, [C.c_void_p, _u8p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                     C.POINTER(SgMapCallbacks), C.POINTER(C.c_int32), C.POINTER(SgFrontendStats)]),
     "sg_frontend_features": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sg_frontend_describe": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _fp, _ip, _u64p, _ip, _ip]),
 }
 
 

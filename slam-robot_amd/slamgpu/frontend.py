@@ -16,7 +16,7 @@ import numpy as np
 from .capi import (ADD_OBS_CB, ADD_POINT_CB, FRAME_POSE_CB, POINT_STATE_CB, SET_KEYFRAME_CB, UPDATE_FRAMES_CB,
                    SgDeviceOptions, SgFrontendStats, SgMapCallbacks, check, load_library)
 from .scene import MapArrays
-from .tracker import default_tracker_options
+from .tracker import default_tracker_options, describe_call
 
 NO_BASELINE, NO_OBSERVATIONS, MISMATCHED, BAD_LOCATION = 1, 2, 3, 0
 
@@ -121,6 +121,11 @@ class Matcher:
                                             ids.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(cap)),
               "sg_frontend_features")
         return pts, ids
+
+    def Describe(self, frame: int, xy, levels=None):
+        """HessianTracker.Describe on the pyramid of the keyframe view held for `frame` (sg_frontend_describe):
+        (desc uint64 (n, 4), angle_bin, status).  Raises when no view of that frame is held."""
+        return describe_call(self.lib.sg_frontend_describe, self.h, frame, xy, levels, "sg_frontend_describe")
 
     def Track(self, img: np.ndarray, frame: int, camera: int, m: MapArrays, update_frames=None) -> bool:
         """Matcher::Track(img, frame, camera, map, update_frames).  img: (h, w, 3) uint8, cv::Mat BGR order."""

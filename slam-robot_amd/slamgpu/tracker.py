@@ -32,6 +32,21 @@ def default_tracker_options(**kw) -> SgTrackerOptions:
     return o
 
 
+def describe_call(fn, handle, key: int, xy, levels, what: str):
+    """sg_tracker_describe / sg_frontend_describe (`key` = slot / frame): (desc uint64 (n, 4), angle_bin, status)."""
+    xy = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+    n = xy.shape[0]
+    lv = None if levels is None else np.ascontiguousarray(levels, dtype=np.int32).reshape(-1)
+    if lv is not None and lv.shape[0] != n:
+        raise ValueError("one level per keypoint")
+    desc = np.zeros((n, 4), np.uint64)
+    ang = np.zeros(n, np.int32)
+    st = np.zeros(n, np.int32)
+    check(fn(handle, key, n, xy.ctypes.data_as(_fp), None if lv is None else lv.ctypes.data_as(_ip),
+             desc.ctypes.data_as(C.POINTER(C.c_uint64)), ang.ctypes.data_as(_ip), st.ctypes.data_as(_ip)), what)
+    return desc, ang, st
+
+
 class HessianTracker:
     def __init__(self, window: int = 13, depth: int = 6, device: int = 0, max_images: int = 8, **kw):
         self.lib = load_library()
@@ -121,6 +136,18 @@ class HessianTracker:
         t, p = C.c_double(), C.c_double()
         check(self.lib.sg_tracker_kernel_ms(self.h, C.byref(t), C.byref(p)), "kernel_ms")
         return t.value, p.value
+
+    def Describe(self, slot: int, xy, levels=None):
+        """Oriented 256-bit descriptors (sg_tracker_describe) of the keypoints xy (n, 2), level-0 pixels, each on
+        pyramid level levels[i] (None = level 0) of `slot`.  Returns (desc uint64 (n, 4), angle_bin (n), status (n):
+        0 OK, 1 BORDER with a zero descriptor and angle_bin -1); the rows feed hamming_match / MatchByProjection."""
+        return describe_call(self.lib.sg_tracker_describe, self.h, slot, xy, levels, "sg_tracker_describe")
+
+    def describe_ms(self) -> float:
+        """Kernel time of the last Describe launch (HIP events)."""
+        ms = C.c_double()
+        check(self.lib.sg_tracker_describe_ms(self.h, C.byref(ms)), "sg_tracker_describe_ms")
+        return ms.value
 
     def TrackFeature(self, from_slot: int, to_slot: int, from_xy, to_xy=None, levels=None):
         """One-directional TrackFeature of this tracker's mode (hessian.h:243-264 / klt.h:403-424 /
