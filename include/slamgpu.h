@@ -934,6 +934,66 @@ int sg_tracker_describe(sg_tracker* t, int32_t slot, int32_t n, const float* xy 
 /* HIP events around the last describe launch of this tracker. */
 int sg_tracker_describe_ms(sg_tracker* t, double* kernel_ms);
 
+/* Detect keypoints: FAST-9 corners on the blurred float pyramid of slot `slot`, spread over the image by 32 x 32
+ * cells, on any range of levels in one device launch.  The output goes straight into sg_tracker_describe.  The rules
+ * apply to each selected level l, whose image I has size w x h.  Every decision is an fp32 comparison, a min or a
+ * max; there is no sum and no product, so the answer has no rounding freedom (csrc/detect_math.h holds the shared
+ * arithmetic).
+ *   ring       the 16 offsets (dx, dy) of the radius-3 Bresenham circle, clockwise from the top:
+ *              (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2)
+ *              (-1,-3).
+ *   score      d_i = I(ring_i) - I(p), one fp32 subtraction;
+ *              s(p) = max( max_k min_{j<9} d_{(k+j)&15} , max_k min_{j<9} (-d_{(k+j)&15}) ): the largest threshold at
+ *              which p is still a FAST-9 corner, bright or dark.  Defined wherever the ring fits, which with
+ *              border >= 4 covers every neighbour of an admissible pixel.
+ *   candidate  p = (x, y) is admissible when border <= x <= w-1-border and border <= y <= h-1-border (a level too
+ *              small for that yields nothing).  An admissible p is a candidate when s(p) > t_lo and it survives the
+ *              3 x 3 non-maximum suppression: s(p) > s of the four neighbours earlier in row-major order (the three
+ *              above and the left one) and s(p) >= s of the four later ones.  Neighbours outside the admissible
+ *              rectangle take part with their real score.  No two 8-adjacent pixels both survive, so a cell holds at
+ *              most 256 candidates.
+ *   cells      32 x 32 level pixels, anchored at pixel (0, 0) of the level; the last column and row may be partial.
+ *              If a cell has a candidate with s > t_hi, only those candidates are eligible; otherwise all its
+ *              candidates are, and a cell that has candidates but none above t_hi counts in low_cells (a cell
+ *              without candidates is on neither branch).  The cell keeps its per_cell best eligible candidates by
+ *              (s descending, pixel index y w + x ascending).
+ *   output     xy = (x 2^l, y 2^l), exact in fp32, so that sg_tracker_describe recovers exactly (x, y) on level l;
+ *              levels = l; score = s.  Order: level ascending, then cell row-major, then rank within the cell.
+ *   cap        with max_keypoints > 0 and more keypoints than that, the max_keypoints best of the call by
+ *              (s descending, level ascending, pixel index ascending) stay; the output order is unchanged.
+ *   filling    *count is always the full number of keypoints (after the cap of max_keypoints); at most `cap` of
+ *              them, the first in output order, are written, and array elements past those are left as they were.
+ *              cap == 0 with null arrays is allowed.  cap >= (sum of the selected levels' cells) x per_cell always
+ *              holds everything.
+ *   per_level  [depth] records (may be NULL): every level's width and height; for the selected levels also the
+ *              number of cells, the candidates before selection, low_cells, and the keypoints after the cap; the
+ *              other fields of levels that were not selected are 0.
+ * The same bits come out on every run and wherever the image sits in a slot: no atomics, no order-dependent step.
+ * SG_EINVAL, found on the host before the device is touched and with nothing written: a null handle, options or
+ * count; cap < 0; null xy or levels with cap > 0; a slot out of range or never set; first_level outside
+ * 0..depth-1; num_levels < 0 or first_level + num_levels > depth; a threshold that is not finite or is negative, or
+ * min_threshold > threshold; border outside 4..64; per_cell outside 1..16; max_keypoints < 0.
+ * Not built: sub-pixel refinement, a Harris ranking, a quadtree distribution; the keypoints come back to the host. */
+typedef struct sg_detect_options {
+  float threshold;        /* t_hi, intensity units of the pyramid (grey / 255); default 20/255 */
+  float min_threshold;    /* t_lo, 0 <= t_lo <= t_hi, finite; default 7/255 */
+  int32_t first_level;    /* default 0 */
+  int32_t num_levels;     /* 0 = every level from first_level to depth - 1 */
+  int32_t border;         /* 4..64 level pixels; default 15 (sg_tracker_describe's) */
+  int32_t per_cell;       /* 1..16; default 4 */
+  int32_t max_keypoints;  /* 0 = no cap */
+} sg_detect_options;
+typedef struct sg_detect_level {
+  int32_t width, height, cells, candidates, low_cells, keypoints;
+} sg_detect_level;
+void sg_detect_options_default(sg_detect_options* o);
+int sg_tracker_detect(sg_tracker* t, int32_t slot, const sg_detect_options* o, int32_t cap,
+                      float* xy /*[2 cap], level-0 pixels*/, int32_t* levels /*[cap]*/,
+                      float* score /*[cap], may be NULL*/, int32_t* count,
+                      sg_detect_level* per_level /*[depth], may be NULL*/);
+/* HIP events around the last detect launch of this tracker. */
+int sg_tracker_detect_ms(sg_tracker* t, double* kernel_ms);
+
 /* ------------------------------------------------------------------------------------------------
  * All-pairs 256-bit descriptor matching (the matcher's brute-force descriptor distance; BASELINE config 4).
  * Descriptors are 4 x uint64 per row.  Per query row: best_idx = argmin over train rows of
@@ -1019,6 +1079,10 @@ int sg_frontend_features(sg_frontend* f, int32_t* points, int32_t* ids, int32_t*
  * the view only: sg_frontend_track behaves as if the call had not been made. */
 int sg_frontend_describe(sg_frontend* f, int32_t frame, int32_t n, const float* xy, const int32_t* levels,
                          uint64_t* desc, int32_t* angle_bin, int32_t* status);
+/* sg_tracker_detect on the pyramid of the keyframe view held for `frame`, under sg_frontend_describe's rule:
+ * SG_EINVAL when no view of that frame is held; it reads the view only. */
+int sg_frontend_detect(sg_frontend* f, int32_t frame, const sg_detect_options* o, int32_t cap, float* xy,
+                       int32_t* levels, float* score, int32_t* count, sg_detect_level* per_level);
 
 #ifdef __cplusplus
 }

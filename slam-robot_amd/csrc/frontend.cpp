@@ -208,6 +208,16 @@ class Frontend {
     trk_->Describe(view->slot, n, xy, levels, desc, angle_bin, status);
   }
 
+  // sg_tracker_detect on the same view, under the same rule.
+  void Detect(int frame, const sg_detect_options& o, int cap, float* xy, int32_t* levels, float* score, int32_t* count,
+              sg_detect_level* per_level) {
+    const View* view = nullptr;
+    for (auto& v : views_)
+      if (v.frame == frame) view = &v;
+    SG_REQUIRE(view, SG_EINVAL, "no keyframe view of that frame is held");
+    trk_->Detect(view->slot, o, cap, xy, levels, score, count, per_level);
+  }
+
   int Features(int32_t* points, int32_t* ids, int cap) const {
     int i = 0;
     for (auto& f : features_) {
@@ -377,6 +387,14 @@ int sg_frontend_describe(sg_frontend* f, int32_t frame, int32_t n, const float* 
   SG_CAPI_BEGIN
   SG_REQUIRE(f, SG_EINVAL, "null handle");
   f->f->Describe(frame, n, xy, levels, desc, angle_bin, status);
+  SG_CAPI_END
+}
+
+int sg_frontend_detect(sg_frontend* f, int32_t frame, const sg_detect_options* o, int32_t cap, float* xy,
+                       int32_t* levels, float* score, int32_t* count, sg_detect_level* per_level) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(f && o, SG_EINVAL, "null handle or options");
+  f->f->Detect(frame, *o, cap, xy, levels, score, count, per_level);
   SG_CAPI_END
 }
 

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "dbuf.h"
+#include "detect_math.h"
 
 namespace sg {
 
@@ -51,6 +52,10 @@ class Tracker {
   void Describe(int slot, int n, const float* xy, const int32_t* levels, uint64_t* desc, int32_t* angle_bin,
                 int32_t* status);
   double describe_ms() const { return describe_ms_; }
+  // sg_tracker_detect (detect.hip): FAST-9 keypoints of the selected levels of `slot`, one launch.
+  void Detect(int slot, const sg_detect_options& o, int cap, float* xy, int32_t* levels, float* score, int32_t* count,
+              sg_detect_level* per_level);
+  double detect_ms() const { return detect_ms_; }
   double track_ms() const { return track_ms_; }
   // diagnostics: accumulated per-phase cycles of k_track_fb since the last call (SG_TRK_STAMP=1), kTrkStamps
   std::vector<unsigned long long> Stamps();
@@ -68,7 +73,7 @@ class Tracker {
   sg_tracker_options opt_;
   sg_device_options dev_;
   hipStream_t stream_ = nullptr;
-  hipEvent_t ev_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // track, pyramid, describe pairs
+  hipEvent_t ev_[8] = {};   // track, pyramid, describe, detect pairs
   std::vector<Slot> slots_;
   DBuf<float> mask_, tmp_, tmp2_;
   DBuf<uint8_t> img_;
@@ -93,6 +98,11 @@ class Tracker {
   DBuf<int32_t> desc_lv_, desc_bin_, desc_st_;
   DBuf<uint64_t> desc_out_;
   double describe_ms_ = 0.0;
+  DBuf<uint64_t> det_slots_;        // Detect's cell slots and per-cell counts, and their host copies
+  DBuf<DetCellInfo> det_info_;
+  std::vector<uint64_t> det_slots_h_;
+  std::vector<DetCellInfo> det_info_h_;
+  double detect_ms_ = 0.0;
 };
 
 }  // namespace sg

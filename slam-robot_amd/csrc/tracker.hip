@@ -1377,6 +1377,8 @@ Tracker::Tracker(const sg_tracker_options& o, const sg_device_options& d) : opt_
   SG_HIP_CHECK(hipEventCreate(&ev_[3]));
   SG_HIP_CHECK(hipEventCreate(&ev_[4]));
   SG_HIP_CHECK(hipEventCreate(&ev_[5]));
+  SG_HIP_CHECK(hipEventCreate(&ev_[6]));
+  SG_HIP_CHECK(hipEventCreate(&ev_[7]));
   slots_.resize(o.max_images);
   // hessian.h:11-30 mask
   const int W = o.window, len = W * W;

@@ -151,4 +151,31 @@ int sg_tracker_describe_ms(sg_tracker* t, double* kernel_ms) {
   SG_CAPI_END
 }
 
+void sg_detect_options_default(sg_detect_options* o) {
+  if (!o) return;
+  *o = sg_detect_options{};
+  o->threshold = 20.0f / 255.0f;
+  o->min_threshold = 7.0f / 255.0f;
+  o->first_level = 0;
+  o->num_levels = 0;
+  o->border = 15;   // sg_tracker_describe's
+  o->per_cell = 4;
+  o->max_keypoints = 0;
+}
+
+int sg_tracker_detect(sg_tracker* t, int32_t slot, const sg_detect_options* o, int32_t cap, float* xy, int32_t* levels,
+                      float* score, int32_t* count, sg_detect_level* per_level) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(t && o, SG_EINVAL, "null handle or options");
+  t->t->Detect(slot, *o, cap, xy, levels, score, count, per_level);
+  SG_CAPI_END
+}
+
+int sg_tracker_detect_ms(sg_tracker* t, double* kernel_ms) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(t && kernel_ms, SG_EINVAL, "null argument");
+  *kernel_ms = t->t->detect_ms();
+  SG_CAPI_END
+}
+
 }  // extern "C"

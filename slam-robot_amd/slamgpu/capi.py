@@ -322,6 +322,19 @@ class SgTrackerOptions(C.Structure):
                 ("max_images", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class SgDetectOptions(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("min_threshold", C.c_float), ("first_level", C.c_int32),
+                ("num_levels", C.c_int32), ("border", C.c_int32), ("per_cell", C.c_int32),
+                ("max_keypoints", C.c_int32)]
+
+
+class SgDetectLevel(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "cells", "candidates", "low_cells", "keypoints")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 _fp = C.POINTER(C.c_float)
 _u8p = C.POINTER(C.c_uint8)
 
@@ -403,6 +416,10 @@ SYMBOLS = {
                                            _fp, _ip, _fp, _ip]),
     "sg_tracker_describe": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _fp, _ip, _u64p, _ip, _ip]),
     "sg_tracker_describe_ms": (C.c_int, [C.c_void_p, _dp]),
+    "sg_detect_options_default": (None, [C.POINTER(SgDetectOptions)]),
+    "sg_tracker_detect": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(SgDetectOptions), C.c_int32, _fp, _ip, _fp, _ip,
+                                    C.POINTER(SgDetectLevel)]),
+    "sg_tracker_detect_ms": (C.c_int, [C.c_void_p, _dp]),
     "sg_matcher_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SgDeviceOptions)]),
     "sg_matcher_destroy": (None, [C.c_void_p]),
     "sg_hamming_match": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_uint64), C.c_int32,
@@ -459,6 +476,8 @@ SYMBOLS = {
                                     C.POINTER(SgMapCallbacks), C.POINTER(C.c_int32), C.POINTER(SgFrontendStats)]),
     "sg_frontend_features": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sg_frontend_describe": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _fp, _ip, _u64p, _ip, _ip]),
+    "sg_frontend_detect": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(SgDetectOptions), C.c_int32, _fp, _ip, _fp, _ip,
+                                     C.POINTER(SgDetectLevel)]),
 }
 
 

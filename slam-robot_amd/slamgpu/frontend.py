@@ -16,7 +16,7 @@ import numpy as np
 from .capi import (ADD_OBS_CB, ADD_POINT_CB, FRAME_POSE_CB, POINT_STATE_CB, SET_KEYFRAME_CB, UPDATE_FRAMES_CB,
                    SgDeviceOptions, SgFrontendStats, SgMapCallbacks, check, load_library)
 from .scene import MapArrays
-from .tracker import default_tracker_options, describe_call
+from .tracker import default_tracker_options, describe_call, detect_call
 
 NO_BASELINE, NO_OBSERVATIONS, MISMATCHED, BAD_LOCATION = 1, 2, 3, 0
 
@@ -99,6 +99,7 @@ class Matcher:
         dev = SgDeviceOptions(device=device, precision=0, rank=0, nranks=1)
         check(self.lib.sg_frontend_create(C.byref(self.h), C.byref(self.opt), C.byref(dev)), "sg_frontend_create")
         self.last_stats = None
+        self._sizes = {}      # frame -> (w, h) of the image it was tracked with: Detect sizes its arrays from it
 
     def close(self):
         if self.h:
@@ -127,10 +128,18 @@ class Matcher:
         (desc uint64 (n, 4), angle_bin, status).  Raises when no view of that frame is held."""
         return describe_call(self.lib.sg_frontend_describe, self.h, frame, xy, levels, "sg_frontend_describe")
 
+    def Detect(self, frame: int, **options):
+        """HessianTracker.Detect on the pyramid of the keyframe view held for `frame` (sg_frontend_detect):
+        (xy, levels, score, per_level).  Raises when no view of that frame is held."""
+        w, h = self._sizes.get(frame, (1, 1))      # a frame never tracked has no view: the library refuses it
+        return detect_call(self.lib.sg_frontend_detect, self.h, frame, w, h, self.opt.depth, options,
+                           "sg_frontend_detect")
+
     def Track(self, img: np.ndarray, frame: int, camera: int, m: MapArrays, update_frames=None) -> bool:
         """Matcher::Track(img, frame, camera, map, update_frames).  img: (h, w, 3) uint8, cv::Mat BGR order."""
         img = np.ascontiguousarray(img, dtype=np.uint8)
         h, w = img.shape[:2]
+        self._sizes[frame] = (w, h)
         if getattr(m, "frame_keyframe", None) is None:
             m.frame_keyframe = np.zeros(m.num_frames, np.int32)
         pend_X, pend_obs = [], []

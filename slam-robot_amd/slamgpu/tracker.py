@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from .capi import SgDeviceOptions, SgTrackerOptions, check, load_library
+from .capi import SgDetectLevel, SgDetectOptions, SgDeviceOptions, SgTrackerOptions, check, load_library
 
 
 def _dev(device=0):
@@ -45,6 +45,42 @@ def describe_call(fn, handle, key: int, xy, levels, what: str):
     check(fn(handle, key, n, xy.ctypes.data_as(_fp), None if lv is None else lv.ctypes.data_as(_ip),
              desc.ctypes.data_as(C.POINTER(C.c_uint64)), ang.ctypes.data_as(_ip), st.ctypes.data_as(_ip)), what)
     return desc, ang, st
+
+
+def default_detect_options(**kw) -> SgDetectOptions:
+    lib = load_library()
+    o = SgDetectOptions()
+    lib.sg_detect_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError("no detect option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+def detect_cap(w: int, h: int, depth: int, per_cell: int) -> int:
+    """What always holds every keypoint: the 32 x 32 cells of all `depth` levels of a w x h image, times per_cell."""
+    cells = 0
+    for _ in range(depth):
+        cells += ((w + 31) // 32) * ((h + 31) // 32)
+        w, h = (w + 1) // 2, (h + 1) // 2
+    return cells * per_cell
+
+
+def detect_call(fn, handle, key: int, w: int, h: int, depth: int, options: dict, what: str):
+    """sg_tracker_detect / sg_frontend_detect (`key` = slot / frame) on a pyramid of `depth` levels over a w x h
+    image: (xy float32 (n, 2) level-0 pixels, levels int32 (n), score float32 (n), per_level list of dicts)."""
+    o = default_detect_options(**options)
+    cap = detect_cap(w, h, depth, max(1, min(16, o.per_cell)))
+    xy = np.zeros((cap, 2), np.float32)
+    lv = np.zeros(cap, np.int32)
+    sc = np.zeros(cap, np.float32)
+    n = C.c_int32()
+    per = (SgDetectLevel * depth)()
+    check(fn(handle, key, C.byref(o), cap, xy.ctypes.data_as(_fp), lv.ctypes.data_as(_ip), sc.ctypes.data_as(_fp),
+             C.byref(n), per), what)
+    k = min(n.value, cap)
+    return xy[:k].copy(), lv[:k].copy(), sc[:k].copy(), [p.as_dict() for p in per]
 
 
 class HessianTracker:
@@ -148,6 +184,30 @@ class HessianTracker:
         ms = C.c_double()
         check(self.lib.sg_tracker_describe_ms(self.h, C.byref(ms)), "sg_tracker_describe_ms")
         return ms.value
+
+    def Detect(self, slot: int, **options):
+        """FAST-9 keypoints (sg_tracker_detect) on the pyramid of `slot`, spread by 32 x 32 cells; options are
+        sg_detect_options' fields (threshold, min_threshold, first_level, num_levels, border, per_cell,
+        max_keypoints).  Returns (xy (n, 2) level-0 pixels, levels (n), score (n), per_level: one dict per pyramid
+        level); xy and levels go straight into Describe."""
+        w, h = C.c_int32(), C.c_int32()
+        check(self.lib.sg_tracker_get_level(self.h, slot, 0, None, C.byref(w), C.byref(h)), "get_level")
+        return detect_call(self.lib.sg_tracker_detect, self.h, slot, w.value, h.value, self.opt.depth, options,
+                           "sg_tracker_detect")
+
+    def detect_ms(self) -> float:
+        """Kernel time of the last Detect launch (HIP events)."""
+        ms = C.c_double()
+        check(self.lib.sg_tracker_detect_ms(self.h, C.byref(ms)), "sg_tracker_detect_ms")
+        return ms.value
+
+    def DetectAndDescribe(self, slot: int, **options):
+        """Detect, then Describe on the result; only the keypoints whose descriptor is SG_DESC_OK are returned
+        (with the default border of 15 that is all of them): (xy, levels, score, desc uint64 (n, 4), angle_bin)."""
+        xy, lv, sc, _ = self.Detect(slot, **options)
+        desc, ang, st = self.Describe(slot, xy, lv)
+        ok = st == 0
+        return xy[ok], lv[ok], sc[ok], desc[ok], ang[ok]
 
     def TrackFeature(self, from_slot: int, to_slot: int, from_xy, to_xy=None, levels=None):
         """One-directional TrackFeature of this tracker's mode (hessian.h:243-264 / klt.h:403-424 /
