@@ -1011,6 +1011,67 @@ int sg_hamming_load(sg_matcher* m, const uint64_t* query, int32_t nq, const uint
 int sg_hamming_run(sg_matcher* m, int32_t repeats);
 int sg_hamming_results(sg_matcher* m, int32_t* best_idx, int32_t* best_dist, int32_t* second_dist,
                        double* kernel_ms);
+
+/* Keyframe retrieval: which keyframe does this frame look like?  A device-resident database of keyframe descriptor
+ * sets on the sg_matcher handle, and a query that matches one frame's descriptors against every stored set in one
+ * call: three launches whatever the number of sets.  The query scores every set by its one-to-one matches, ranks the
+ * sets, and returns the keypoint-to-keypoint matches of the best k.  Brute force and exact: integers only, the same
+ * bits on every run.
+ *
+ * sg_matcher_db_add appends one keyframe's n descriptors (4 x uint64 per row) as set S; sets are numbered 0, 1, 2, ...
+ * in order of addition and the number is returned in *set_id (may be NULL).  n == 0 makes an empty set.  The
+ * descriptors are uploaded once and stay on the device; the device buffer grows geometrically, the old contents
+ * moved by a device-to-device copy on the matcher's stream.  SG_EINVAL, with nothing changed: a null m; n < 0; a null
+ * desc with n > 0; n > 65536; a 4097th set; more than 2^22 descriptors in all (128 MiB).
+ * sg_matcher_db_clear forgets every set (numbering restarts at 0; the device buffer is kept).
+ * sg_matcher_db_count gives the number of sets and of descriptors (either pointer may be NULL).
+ *
+ * sg_matcher_db_query, with S sets of n_s descriptors and nq query rows:
+ *   1. For every set s with skip == NULL or skip[s] == 0 and every query row i: (best_idx, best_dist, second_dist)
+ *      within set s alone by sg_hamming_match's rule: best_idx = argmin of popcount(q XOR t), ties to the lowest
+ *      index within the set; second_dist = the second smallest distance of the multiset, -1 when n_s < 2.  An empty
+ *      set gives no result.
+ *   2. Query i is a candidate for set s when n_s >= 1, best_dist <= max_dist and either second_dist < 0 or
+ *      100 best_dist <= ratio_percent second_dist (sg_slam_match_by_projection's acceptance rule, in integers).
+ *   3. One-to-one within a set: a descriptor that is best_idx of several candidates goes to the candidate with the
+ *      smallest (best_dist, i); the other claimants are unmatched in that set (no fall-back to a second choice).
+ *   4. score[s] = the number of matched queries of set s (= the number of claimed descriptors); 0 for an empty set,
+ *      -1 for a skipped one.
+ *   5. Ranking, on the host: the sets with score >= min_score that are not skipped, by (score descending, set index
+ *      ascending); top_set[r], top_score[r] hold the r-th of them for r < k, the remaining entries -1, -1.
+ *   6. For each rank r with top_set[r] >= 0: match[r nq + i] = the index within the set of the descriptor matched to
+ *      query i, or -1; match_dist[r nq + i] its distance, or -1.  Rows of unfilled ranks are -1.  Only the rows of
+ *      the ranked sets are copied back from the device.  match and match_dist may be NULL.
+ *   - A set's score and match row depend on the query, the options and that set's descriptors only: not on its
+ *     position in the database, on the other sets or on skip; they are reproducible bit for bit.
+ *   - With nq == 0 or S == 0 nothing is launched and the outputs are the empty answers: score 0 (-1 for a skipped
+ *     set), ranked by rule 5 like any other scores (so nothing ranks unless min_score == 0).
+ *   - sg_hamming_load / run / results / match on the same handle are independent of the database, and the reverse.
+ *   - SG_EINVAL, all found on the host before anything is launched, with nothing written: a null m or options; a
+ *     null score with S > 0; nq < 0; a null query with nq > 0; k < 0; a null top_set or top_score with k > 0;
+ *     max_dist outside 0..256, ratio_percent outside 1..100, min_score < 0; nq > 2^20; S nq > 2^23.
+ *   - Device workspace of a query, besides the database (32 bytes per descriptor) and the query: 8 S nq bytes of
+ *     per-(set, query) cells (<= 64 MiB), 4 bytes per database descriptor of claims (<= 16 MiB), 4 S bytes of scores,
+ *     and 8 bytes per (slice, query) of partials, <= 128 MiB: a set is cut into slices of 1024 descriptors, and the
+ *     slice length doubles until slices x nq <= 2^24.  Buffers are kept between calls and grow geometrically.
+ * sg_matcher_db_query_ms: HIP-event time of the last query's launches (0 when it launched nothing); SG_EINVAL before
+ * the first query.
+ * Not in scope: removing a single set (use skip); a vocabulary or an inverted index; geometric verification (that is
+ * sg_slam_relative_poses / sg_slam_localize_frames); storing descriptors in sg_map; a symmetric cross-check. */
+int sg_matcher_db_add(sg_matcher* m, const uint64_t* desc /*[4 n]*/, int32_t n, int32_t* set_id);
+int sg_matcher_db_clear(sg_matcher* m);
+int sg_matcher_db_count(const sg_matcher* m, int32_t* num_sets, int64_t* num_descriptors);
+typedef struct sg_retrieve_options {
+  int32_t max_dist;        /* 0..256 */
+  int32_t ratio_percent;   /* 1..100 */
+  int32_t min_score;       /* >= 0: a set ranks only with score >= min_score */
+} sg_retrieve_options;
+void sg_retrieve_options_default(sg_retrieve_options* o);   /* 64, 80, 1 */
+int sg_matcher_db_query(sg_matcher* m, const uint64_t* query /*[4 nq]*/, int32_t nq,
+                        const sg_retrieve_options* options, const uint8_t* skip /*[S] or NULL*/,
+                        int32_t* score /*[S]*/, int32_t k, int32_t* top_set /*[k]*/, int32_t* top_score /*[k]*/,
+                        int32_t* match /*[k nq], may be NULL*/, int32_t* match_dist /*[k nq], may be NULL*/);
+int sg_matcher_db_query_ms(sg_matcher* m, double* kernel_ms);
 int sg_slam_set_options(sg_slam* s, const sg_solver_options* o);
 
 /* LocalMap maintenance on the device, run on the residuals sg_slam_reproject_map wrote (main.cpp:584-599).

@@ -19,6 +19,8 @@
 //     in slice order.
 // The VALU popcount kernel this replaces (scalar-load train operands, 19 ops per pair) ran 70 us at
 // 10k x 10k and was bound by v_bcnt issue.
+// The expansion, the key rule and the tile (expand16, ham_take, ham_merge, ham_tile) are in hamming_tile.h, shared
+// with retrieve.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,84 +29,12 @@
 
 #include "common.h"
 #include "dbuf.h"
+#include "hamming_tile.h"
+#include "matcher_handle.h"
 
 namespace sg {
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));   // 16 int8 (one MFMA A/B fragment) or 4 int32 (C/D)
-
-constexpr int kHmThreads = 512;              // 8 waves: 4 query groups x 2 train halves
-constexpr int kHmQ = 256;                    // queries per workgroup
-constexpr int kHmTile = 128;                 // train descriptors per LDS tile
-constexpr int kHmPitch = 272;                // LDS bytes per descriptor row (256 + 16)
-constexpr int kKeyShift = 22;                // slice index bits of the packed key (slices <= 2^22)
-constexpr unsigned kKeyInf = 0xFFFFFFFFu;
-
-// 4 bits -> 4 bytes of +-1: spread bit i to byte i ((n * 0x204081) & 0x01010101, no carries: the shifted
-// copies do not overlap), make each set byte 0xFF ((s << 8) - s), then pick +1 / -1 per byte with v_bfi.
-// pos: the byte of a set bit (+1 for queries, -1 for the train side); the clear bits get the other sign.
-__device__ __forceinline__ int expand4(unsigned nib, unsigned pos, unsigned negv) {
-  const unsigned s = __umul24(nib, 0x204081u) & 0x01010101u;
-  const unsigned m = (s << 8) - s;
-  return (int)((m & pos) | (~m & negv));   // v_bfi_b32
-}
-// 16 bits -> one A/B fragment (16 int8)
-__device__ __forceinline__ v4i expand16(unsigned b, unsigned pos, unsigned negv) {
-  v4i w;
-  w[0] = expand4(b & 15u, pos, negv);
-  w[1] = expand4((b >> 4) & 15u, pos, negv);
-  w[2] = expand4((b >> 8) & 15u, pos, negv);
-  w[3] = expand4((b >> 12) & 15u, pos, negv);
-  return w;
-}
-
-__device__ __forceinline__ unsigned umed3(unsigned a, unsigned b, unsigned c) {
-  unsigned r;
-  asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-
-__device__ __forceinline__ void ham_take(unsigned key, unsigned& m1, unsigned& m2) {
-  m2 = umed3(m1, key, m2);   // second smallest (m1 <= m2)
-  m1 = min(m1, key);
-}
-
-__device__ __forceinline__ void ham_merge(unsigned& m1, unsigned& m2, unsigned o1, unsigned o2) {
-  const unsigned n2 = min(max(m1, o1), min(m2, o2));
-  m1 = min(m1, o1);
-  m2 = n2;
-}
-
-// qb / tb: the descriptors' bits, 16 uint16 (256 bits) per descriptor; expanded to +-1 int8 on the way in
-// (A fragments once per workgroup, B tiles into LDS).
-template <bool kPartial>
-__device__ __forceinline__ void ham_tile(const v4i (&a)[4][4], const unsigned char* tile, int wi, int li, int g,
-                                         int tbase, int cnt, unsigned (&m1)[4][4], unsigned (&m2)[4][4]) {
-  const v4i cinit = {256, 256, 256, 256};
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct) {
-    const int row = 64 * wi + 16 * ct + li;
-    v4i acc[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const v4i bf = *reinterpret_cast<const v4i*>(tile + row * kHmPitch + 64 * k + 16 * g);
-#pragma unroll
-      for (int rt = 0; rt < 4; ++rt)
-        acc[rt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[rt][k], bf, k == 0 ? cinit : acc[rt], 0, 0, 0);
-    }
-    // acc[rt][r] = 2 h of query 16 rt + 4 g + r and train descriptor tbase + row (slice index)
-    const unsigned idx = (unsigned)(tbase + row);
-#pragma unroll
-    for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        unsigned key = ((unsigned)acc[rt][r] << kKeyShift) | idx;
-        if (kPartial) key = (int)idx < cnt ? key : kKeyInf;
-        ham_take(key, m1[rt][r], m2[rt][r]);
-      }
-  }
-}
 
 __global__ __launch_bounds__(kHmThreads) void k_hamming_slices(const uint16_t* __restrict__ qb, int nq,
                                                                const uint16_t* __restrict__ tb, int nt, int slice_len,
@@ -240,6 +170,8 @@ class HammingMatcher {
     if (stream_) (void)hipStreamDestroy(stream_);
   }
 
+  hipStream_t stream() const { return stream_; }
+
   void Load(const uint64_t* q, int nq, const uint64_t* t, int nt) {
     SG_REQUIRE(nq >= 0 && nt >= 0 && (nq == 0 || q) && (nt == 0 || t), SG_EINVAL, "bad descriptors");
     SG_HIP_CHECK(hipSetDevice(dev_.device));
@@ -303,9 +235,11 @@ class HammingMatcher {
 
 }  // namespace sg
 
-struct sg_matcher {
-  std::unique_ptr<sg::HammingMatcher> m;
-};
+sg_matcher::sg_matcher() = default;
+sg_matcher::~sg_matcher() {
+  sg::DeleteKeyframeDb(db);   // its buffers and events, while the stream still exists
+  db = nullptr;
+}
 
 extern "C" {
 
@@ -317,6 +251,8 @@ int sg_matcher_create(sg_matcher** out, const sg_device_options* dev) {
   if (dev) d = *dev;
   auto h = std::make_unique<sg_matcher>();
   h->m.reset(new sg::HammingMatcher(d));
+  h->dev = d;
+  h->stream = h->m->stream();
   *out = h.release();
   SG_CAPI_END
 }

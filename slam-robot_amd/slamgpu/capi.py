@@ -171,6 +171,10 @@ class SgMatchOptions(C.Structure):
                 ("ratio_percent", C.c_int32), ("skip_observed", C.c_int32)]
 
 
+class SgRetrieveOptions(C.Structure):
+    _fields_ = [("max_dist", C.c_int32), ("ratio_percent", C.c_int32), ("min_score", C.c_int32)]
+
+
 class SgMatchResult(C.Structure):
     _fields_ = [("num_keypoints", C.c_int32), ("num_projected", C.c_int32), ("num_with_candidates", C.c_int32),
                 ("num_matched", C.c_int32)]
@@ -427,6 +431,13 @@ SYMBOLS = {
     "sg_hamming_load": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_uint64), C.c_int32]),
     "sg_hamming_run": (C.c_int, [C.c_void_p, C.c_int32]),
     "sg_hamming_results": (C.c_int, [C.c_void_p, _ip, _ip, _ip, _dp]),
+    "sg_matcher_db_add": (C.c_int, [C.c_void_p, _u64p, C.c_int32, _ip]),
+    "sg_matcher_db_clear": (C.c_int, [C.c_void_p]),
+    "sg_matcher_db_count": (C.c_int, [C.c_void_p, _ip, C.POINTER(C.c_int64)]),
+    "sg_retrieve_options_default": (None, [C.POINTER(SgRetrieveOptions)]),
+    "sg_matcher_db_query": (C.c_int, [C.c_void_p, _u64p, C.c_int32, C.POINTER(SgRetrieveOptions),
+                                      C.POINTER(C.c_uint8), _ip, C.c_int32, _ip, _ip, _ip, _ip]),
+    "sg_matcher_db_query_ms": (C.c_int, [C.c_void_p, _dp]),
     "sg_slam_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SgDeviceOptions)]),
     "sg_slam_destroy": (None, [C.c_void_p]),
     "sg_slam_solve_frames": (C.c_int, [C.c_void_p, C.POINTER(SgMap), C.c_int32, C.c_int32, C.c_double,
