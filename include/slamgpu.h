@@ -742,6 +742,71 @@ int sg_slam_match_by_projection(sg_slam* s, const sg_map* map, const int32_t* fr
                                 int32_t* num_candidates /*[K], may be NULL*/,
                                 sg_match_result* results /*[n], may be NULL*/);
 
+/* Match along epipolar lines: which still-unmatched keypoints of two posed frames are the same new landmark?
+ * sg_slam_match_by_projection finds only points the map already has, and sg_hamming_match ignores geometry.  After a
+ * keyframe is inserted, this call pairs the keypoints of frame a with those of frame b along the epipolar line their
+ * stored poses give; sg_slam_triangulate_points then makes the landmarks.  All pairs of a call run in three launches.
+ * Pair i = (pairs[2 i], pairs[2 i + 1]) brings its own keypoints: rows a_offset[i] .. a_offset[i + 1] of the a arrays
+ * and b_offset[i] .. b_offset[i + 1] of the b arrays (KA = a_offset[n], KB = b_offset[n]), level-0 pixels, 256-bit
+ * descriptors (4 x u64) and, optionally, the pyramid levels that sg_frontend_detect returns.  A frame listed in several
+ * pairs is given its keypoints each time.
+ *   1. Pair record, on the host in fp64: R_a and R_b from the stored quaternions by the matrix of ProjectJacobian
+ *      (csrc/project_math.h; the quaternion is not normalised), R = R_b R_a^T, tr = R_b (t_a - t_b), E = [tr]x R
+ *      (row-major), ifa = {1 / fx_a, 1 / fy_a} and ifb likewise: the map's convention p = R(q) (X - t W).  The pair is
+ *      degenerate when an entry of E, R or tr is not finite or every entry of E is zero; it then has no candidates and
+ *      results[i].degenerate = 1.
+ *   2. Per keypoint: x = UndistortPixel(k_cam, pixel).  a side: l = E (x_a, 1), na = (l0 ifb0)^2 + (l1 ifb1)^2,
+ *      g = R (x_a, 1).  b side: m = E^T (x_b, 1), nb = (m0 ifa0)^2 + (m1 ifa1)^2.
+ *   3. b keypoint j is a candidate of a keypoint k when, in this order and with every comparison false on a NaN:
+ *      the gate: r = x_b0 l0 + x_b1 l1 + l2, den = na + nb, den > 0 and r r <= tol_px^2 4^L den with L the larger of
+ *      the two levels (0 without levels): RelSampson of csrc/relpose_math.h without the division; the depths: with
+ *      f_b = (x_b, 1), RelDepths' det > 0 and the numerators of both depths > 0; and, with min_parallax > 0,
+ *      RelParallax(g, x_b) >= min_parallax.
+ *   4. num_candidates[k] is the number of candidates; best_kp[k] the candidate with the smallest (popcount(a XOR b),
+ *      j), j being the b keypoint's index within the pair; best_dist[k] that popcount; second_dist[k] the second
+ *      smallest distance as a multiset (equal to best_dist on a tie), -1 with fewer than two candidates.  The empty
+ *      answers are -1, -1, -1, 0.
+ *   5. match[k], decided on the host by sg_slam_match_by_projection's rule within each pair: accepted when best_kp >=
+ *      0, best_dist <= max_dist and either second_dist < 0 or 100 best_dist <= ratio_percent second_dist; a b keypoint
+ *      claimed by several accepted a keypoints goes to the smallest (best_dist, a index), the others get -1.  match[k]
+ *      is a b index within the pair, or -1.
+ *   - A pair's results do not depend on its position in the call and are reproducible bit for bit.  A pair without a
+ *     or without b keypoints gives the empty answers; when every pair is empty or degenerate nothing is launched.  The
+ *     map is never written; sg_slam_iterations, sg_slam_error and sg_slam_last_summary do not move.  No communicator is
+ *     involved: rank-local on a sharded handle.  best_kp, best_dist, second_dist, num_candidates and results may be
+ *     NULL.
+ *   - SG_EINVAL, all found on the host before the device is touched, with nothing written: a null s, map, options or
+ *     match; n < 0; with n > 0 a null pairs, a_offset or b_offset; a null xy or desc array whose count is above 0; only
+ *     one of a_level and b_level given; a level outside 0..7; an offset array that does not start at 0 or decreases; a
+ *     frame index out of range; a == b in a pair; a frame whose camera index is out of range; a map whose poses or
+ *     cameras cannot be read; tol_px not above 0 or not finite; min_parallax negative or not finite; max_dist outside
+ *     0..256; ratio_percent outside 1..100; KA or KB above 2^20; partial results above 128 MiB: the sum over the pairs
+ *     of (a keypoints) x ceil(b keypoints / 512) above 2^23 (split the pairs over calls).  n == 0 returns SG_OK before
+ *     the handle or the device is touched.
+ * Not in scope: octave-consistency or orientation tests; an exclusion zone around the epipole (the parallax gate is the
+ * guard); a symmetric cross-check; writing points or observations into the map; a spatial index. */
+typedef struct sg_epipolar_options {
+  double tol_px;          /* > 0 and finite: the gate, in ideal pixels (Sampson) */
+  double min_parallax;    /* rad, >= 0 and finite; 0: no parallax test */
+  int32_t max_dist;       /* 0..256 */
+  int32_t ratio_percent;  /* 1..100 */
+} sg_epipolar_options;
+
+typedef struct sg_epipolar_result {
+  int32_t num_a, num_b, num_with_candidates, num_matched, degenerate;
+} sg_epipolar_result;
+
+void sg_epipolar_options_default(sg_epipolar_options* o);   /* 2.0, 0.0, 64, 80 */
+int sg_slam_match_epipolar(sg_slam* s, const sg_map* map, const int32_t* pairs /*[2n]: frame a, frame b*/, int32_t n,
+                           const int32_t* a_offset /*[n+1]*/, const double* a_xy /*[2 KA]*/,
+                           const uint64_t* a_desc /*[4 KA]*/, const int32_t* a_level /*[KA] or NULL*/,
+                           const int32_t* b_offset /*[n+1]*/, const double* b_xy /*[2 KB]*/,
+                           const uint64_t* b_desc /*[4 KB]*/, const int32_t* b_level /*[KB] or NULL*/,
+                           const sg_epipolar_options* options, int32_t* match /*[KA]*/,
+                           int32_t* best_kp /*[KA], may be NULL*/, int32_t* best_dist /*[KA], may be NULL*/,
+                           int32_t* second_dist /*[KA], may be NULL*/, int32_t* num_candidates /*[KA], may be NULL*/,
+                           sg_epipolar_result* results /*[n], may be NULL*/);
+
 /* Pose-graph optimisation: spread a loop closure over the frames.  sg_slam_align_points gives the similarity that
  * joins two pieces of a map, and sg_map_apply_similarity moves one piece rigidly; but the drift of a long run is not a
  * rigid offset of one piece.  This call distributes it over the trajectory, scale included, so that the window solve

@@ -10,6 +10,7 @@
 #include <memory>
 
 #include "ba_align.h"
+#include "ba_epipolar.h"
 #include "ba_match.h"
 #include "ba_points.h"
 #include "ba_pose.h"
@@ -37,6 +38,7 @@ struct sg_slam {
   std::unique_ptr<sg::AlignSolver> align;   // created on first use (sg_slam_align_points)
   std::unique_ptr<sg::PoseGraphSolver> posegraph;   // created on first use (sg_slam_optimize_pose_graph)
   std::unique_ptr<sg::MatchSolver> match;   // created on first use (sg_slam_match_by_projection)
+  std::unique_ptr<sg::EpipolarSolver> epipolar;   // created on first use (sg_slam_match_epipolar)
   sg_device_options dev;
   sg_solver_options options;
   int32_t iterations = 0;    // Slam::iterations_ (slam.cpp:517)
@@ -554,6 +556,83 @@ int sg_slam_debug_match_kernel_ms(sg_slam* s, double* ms) {
   SG_CAPI_BEGIN
   SG_REQUIRE(s && ms, SG_EINVAL, "null argument");
   *ms = MatchSolverOf(s).last_kernel_ms();
+  SG_CAPI_END
+}
+
+static sg::EpipolarSolver& EpipolarSolverOf(sg_slam* s) {
+  if (!s->epipolar) s->epipolar.reset(new sg::EpipolarSolver(s->dev, s->solver->stream()));   // one stream per Slam object
+  return *s->epipolar;
+}
+
+// sg_slam_match_epipolar with the device (s) or with the planner's CPU executor (s == nullptr).
+static void MatchEpipolar(sg_slam* s, const sg_map* map, const int32_t* pairs, int32_t n, const int32_t* a_offset,
+                          const double* a_xy, const uint64_t* a_desc, const int32_t* a_level, const int32_t* b_offset,
+                          const double* b_xy, const uint64_t* b_desc, const int32_t* b_level,
+                          const sg_epipolar_options* options, int32_t* match, int32_t* best_kp, int32_t* best_dist,
+                          int32_t* second_dist, int32_t* num_candidates, sg_epipolar_result* results) {
+  sg::EpipolarPlan plan;
+  sg::PlanEpipolar(map, pairs, n, a_offset, a_xy, a_desc, a_level, b_offset, b_xy, b_desc, b_level, options,
+                   &plan);   // every argument check, on the host
+  if (n == 0) return;   // nothing to match: neither the handle nor the device is touched
+  const size_t KA = (size_t)plan.KA;
+  // the empty answers; when no pair is live they stand, and the device is not touched
+  std::vector<int32_t> bk(KA, -1), bd(KA, -1), sd(KA, -1), nc(KA, 0), mt(KA, -1);
+  if (!s)
+    sg::RunEpipolarCpu(plan, a_offset, a_xy, a_desc, a_level, b_offset, b_xy, b_desc, b_level, *options, bk.data(),
+                       bd.data(), sd.data(), nc.data());
+  else if (plan.launch)
+    EpipolarSolverOf(s).Run(plan, a_offset, a_xy, a_desc, a_level, b_offset, b_xy, b_desc, b_level, *options, bk.data(),
+                            bd.data(), sd.data(), nc.data());
+  std::vector<sg_epipolar_result> res((size_t)n, sg_epipolar_result{});
+  sg::ResolveEpipolar(plan, a_offset, b_offset, bk.data(), bd.data(), sd.data(), nc.data(), *options, mt.data(),
+                      res.data());
+  std::copy(mt.begin(), mt.end(), match);
+  if (best_kp) std::copy(bk.begin(), bk.end(), best_kp);
+  if (best_dist) std::copy(bd.begin(), bd.end(), best_dist);
+  if (second_dist) std::copy(sd.begin(), sd.end(), second_dist);
+  if (num_candidates) std::copy(nc.begin(), nc.end(), num_candidates);
+  if (results) std::copy(res.begin(), res.end(), results);
+}
+
+int sg_slam_match_epipolar(sg_slam* s, const sg_map* map, const int32_t* pairs, int32_t n, const int32_t* a_offset,
+                           const double* a_xy, const uint64_t* a_desc, const int32_t* a_level, const int32_t* b_offset,
+                           const double* b_xy, const uint64_t* b_desc, const int32_t* b_level,
+                           const sg_epipolar_options* options, int32_t* match, int32_t* best_kp, int32_t* best_dist,
+                           int32_t* second_dist, int32_t* num_candidates, sg_epipolar_result* results) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s && map && options && match, SG_EINVAL, "null argument");
+  MatchEpipolar(s, map, pairs, n, a_offset, a_xy, a_desc, a_level, b_offset, b_xy, b_desc, b_level, options, match,
+                best_kp, best_dist, second_dist, num_candidates, results);
+  SG_CAPI_END
+}
+
+// Diagnostics (not in the public header): HIP-event time of sg_slam_match_epipolar's three launches, and the same call
+// answered by the planner's CPU executor on the calling thread, without a handle or a device (tools/epipolar_bench.py,
+// tests/test_epipolar_capi.py).
+int sg_slam_debug_epipolar_timing(sg_slam* s, int32_t enable) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s, SG_EINVAL, "null handle");
+  EpipolarSolverOf(s).SetTiming(enable != 0);
+  SG_CAPI_END
+}
+
+int sg_slam_debug_epipolar_kernel_ms(sg_slam* s, double* ms) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(s && ms, SG_EINVAL, "null argument");
+  *ms = EpipolarSolverOf(s).last_kernel_ms();
+  SG_CAPI_END
+}
+
+int sg_debug_match_epipolar_cpu(const sg_map* map, const int32_t* pairs, int32_t n, const int32_t* a_offset,
+                                const double* a_xy, const uint64_t* a_desc, const int32_t* a_level,
+                                const int32_t* b_offset, const double* b_xy, const uint64_t* b_desc,
+                                const int32_t* b_level, const sg_epipolar_options* options, int32_t* match,
+                                int32_t* best_kp, int32_t* best_dist, int32_t* second_dist, int32_t* num_candidates,
+                                sg_epipolar_result* results) {
+  SG_CAPI_BEGIN
+  SG_REQUIRE(map && options && match, SG_EINVAL, "null argument");
+  MatchEpipolar(nullptr, map, pairs, n, a_offset, a_xy, a_desc, a_level, b_offset, b_xy, b_desc, b_level, options,
+                match, best_kp, best_dist, second_dist, num_candidates, results);
   SG_CAPI_END
 }
 

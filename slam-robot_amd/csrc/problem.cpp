@@ -313,6 +313,13 @@ void sg_match_options_default(sg_match_options* o) {
   o->skip_observed = 1;
 }
 
+void sg_epipolar_options_default(sg_epipolar_options* o) {
+  o->tol_px = 2.0;
+  o->min_parallax = 0.0;   // no parallax test
+  o->max_dist = 64;
+  o->ratio_percent = 80;
+}
+
 int sg_map_apply_similarity(sg_map* map, double scale, const double* q, const double* t, const int32_t* frames,
                             int32_t nf, const int32_t* points, int32_t np) {
   SG_CAPI_BEGIN

@@ -20,6 +20,76 @@ def _dev(device=0, precision=0, rank=0, nranks=1):
     return SgDeviceOptions(device=device, precision=precision, rank=rank, nranks=nranks)
 
 
+def _epipolar_side(keypoints, n):
+    """One side's per-pair (pixels, descriptors[, levels]) tuples -> offsets, flat pixels, descriptors, levels."""
+    if len(keypoints) != n:
+        raise ValueError("one (pixels, descriptors[, levels]) tuple per listed pair")
+    xys = [np.ascontiguousarray(k[0], dtype=np.float64).reshape(-1, 2) for k in keypoints]
+    dss = [np.ascontiguousarray(k[1], dtype=np.uint64).reshape(-1, 4) for k in keypoints]
+    if any(len(a) != len(b) for a, b in zip(xys, dss)):
+        raise ValueError("one descriptor per keypoint")
+    with_levels = [len(k) > 2 and k[2] is not None for k in keypoints]
+    if n and any(with_levels) != all(with_levels):
+        raise ValueError("levels for every pair or for none")
+    off = np.zeros(n + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(a) for a in xys])
+    K = int(off[n])
+    xy = np.concatenate(xys).reshape(-1) if K else np.zeros(0)
+    ds = np.concatenate(dss).reshape(-1) if K else np.zeros(0, dtype=np.uint64)
+    lv = None
+    if n and all(with_levels):
+        lvs = [np.ascontiguousarray(k[2], dtype=np.int32).reshape(-1) for k in keypoints]
+        if any(len(a) != len(b) for a, b in zip(xys, lvs)):
+            raise ValueError("one level per keypoint")
+        lv = np.concatenate(lvs) if K else np.zeros(0, dtype=np.int32)
+    return off, xy, ds, lv
+
+
+def _match_epipolar(fn, m, pairs, keypoints_a, keypoints_b, tol_px, min_parallax, max_dist, ratio_percent, what):
+    """Marshal one sg_slam_match_epipolar-shaped call (fn takes the arguments after the handle) and return one
+    result dict per listed pair."""
+    from .capi import SgEpipolarOptions, SgEpipolarResult
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    n = len(pr)
+    ao, axy, ads, alv = _epipolar_side(keypoints_a, n)
+    bo, bxy, bds, blv = _epipolar_side(keypoints_b, n)
+    if (alv is None) != (blv is None):
+        raise ValueError("levels on both sides or on neither")
+    KA = int(ao[n])
+    out = [np.full(max(KA, 1), 7, dtype=np.int32) for _ in range(5)]
+    res = (SgEpipolarResult * max(n, 1))()
+    opt = SgEpipolarOptions(tol_px=tol_px, min_parallax=min_parallax, max_dist=max_dist, ratio_percent=ratio_percent)
+    ms = m.struct()
+    ip, dp, up = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+    lvl = lambda a: None if a is None else a.ctypes.data_as(ip)   # noqa: E731
+    # (empty arrays are passed by address: only the counts decide whether they are read)
+    check(fn(C.byref(ms), pr.ctypes.data_as(ip), n, ao.ctypes.data_as(ip), axy.ctypes.data_as(dp),
+             ads.ctypes.data_as(up), lvl(alv), bo.ctypes.data_as(ip), bxy.ctypes.data_as(dp), bds.ctypes.data_as(up),
+             lvl(blv), C.byref(opt), *[a.ctypes.data_as(ip) for a in out], res), what)
+    names = ("match", "best_kp", "best_dist", "second_dist", "num_candidates")
+    results = []
+    for i in range(n):
+        d = res[i].as_dict()
+        for name, a in zip(names, out):
+            d[name] = a[ao[i]:ao[i + 1]].copy()
+        results.append(d)
+    return results
+
+
+def match_epipolar_cpu(m: MapArrays, pairs, keypoints_a, keypoints_b, tol_px: float = 2.0, min_parallax: float = 0.0,
+                       max_dist: int = 64, ratio_percent: int = 80) -> list:
+    """Slam.MatchEpipolar answered by the planner's CPU executor on the calling thread (a diagnostic entry point of
+    the library: no handle, no device).  Returns what Slam.epipolar_match_results() returns."""
+    from .capi import SgEpipolarOptions, SgEpipolarResult, SgMap
+    fn = load_library().sg_debug_match_epipolar_cpu
+    ip, dp, up = C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(SgMap), ip, C.c_int32, ip, dp, up, ip, ip, dp, up, ip, C.POINTER(SgEpipolarOptions), ip, ip,
+                   ip, ip, ip, C.POINTER(SgEpipolarResult)]
+    return _match_epipolar(fn, m, pairs, keypoints_a, keypoints_b, tol_px, min_parallax, max_dist, ratio_percent,
+                           "match_epipolar_cpu")
+
+
 def problem_from_map_frames(m: MapArrays, num_to_solve: int, num_to_present: int, range_: float = 2.0):
     """Slam::SolveFrames selection + SetupProblem (slam.cpp:257-443) -> ProblemArrays, or None on abort."""
     lib = load_library()
@@ -450,6 +520,28 @@ class Slam:
         num_with_candidates, num_matched and the per-keypoint int32 arrays match, best_point, best_dist, second_dist
         and num_candidates."""
         return list(getattr(self, "_match_results", []))
+
+    def MatchEpipolar(self, m: MapArrays, pairs, keypoints_a, keypoints_b, tol_px: float = 2.0,
+                      min_parallax: float = 0.0, max_dist: int = 64, ratio_percent: int = 80) -> list:
+        """Match along epipolar lines (sg_slam_match_epipolar): which keypoints of frame a and frame b of each listed
+        pair (rows of pairs: frame a, frame b) are the same new landmark, at the poses in m?  keypoints_a and
+        keypoints_b hold one (pixels (k, 2) float64, descriptors (k, 4) uint64[, levels (k,) int32]) tuple per pair:
+        the keypoints of that frame the caller has not matched yet; levels are given for every tuple or for none.  An
+        a keypoint is compared only with the b keypoints within tol_px (ideal pixels, Sampson, scaled by 2^level) of
+        its epipolar line that triangulate in front of both cameras and, with min_parallax > 0 (rad), at that
+        parallax or more.  The accepted, unique matches (max_dist, the ratio test at ratio_percent) come back as one
+        int32 array per pair: per a keypoint, a b keypoint's index within the pair or -1.  The map is not written.
+        epipolar_match_results() has the detail arrays and the per-pair counts."""
+        self._epipolar_results = _match_epipolar(
+            lambda *a: self.lib.sg_slam_match_epipolar(self.h, *a), m, pairs, keypoints_a, keypoints_b, tol_px,
+            min_parallax, max_dist, ratio_percent, "Slam::MatchEpipolar")
+        return [d["match"].copy() for d in self._epipolar_results]
+
+    def epipolar_match_results(self) -> list:
+        """Result dicts of the last MatchEpipolar call, one per listed pair: num_a, num_b, num_with_candidates,
+        num_matched, degenerate and the per-a-keypoint int32 arrays match, best_kp, best_dist, second_dist and
+        num_candidates."""
+        return list(getattr(self, "_epipolar_results", []))
 
     def ApplySimilarity(self, m: MapArrays, scale: float, q, t, frames, points) -> None:
         """sg_map_apply_similarity: moves the listed frames and points of m through Y = scale R(q) X + t in place (on

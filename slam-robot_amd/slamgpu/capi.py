@@ -171,6 +171,19 @@ class SgMatchOptions(C.Structure):
                 ("ratio_percent", C.c_int32), ("skip_observed", C.c_int32)]
 
 
+class SgEpipolarOptions(C.Structure):
+    _fields_ = [("tol_px", C.c_double), ("min_parallax", C.c_double), ("max_dist", C.c_int32),
+                ("ratio_percent", C.c_int32)]
+
+
+class SgEpipolarResult(C.Structure):
+    _fields_ = [("num_a", C.c_int32), ("num_b", C.c_int32), ("num_with_candidates", C.c_int32),
+                ("num_matched", C.c_int32), ("degenerate", C.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class SgRetrieveOptions(C.Structure):
     _fields_ = [("max_dist", C.c_int32), ("ratio_percent", C.c_int32), ("min_score", C.c_int32)]
 
@@ -472,6 +485,10 @@ SYMBOLS = {
     "sg_slam_match_by_projection": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32, _ip, _dp, _u64p, _ip,
                                               C.c_int32, _u64p, C.POINTER(SgMatchOptions), _ip, _ip, _ip, _ip, _ip,
                                               C.POINTER(SgMatchResult)]),
+    "sg_epipolar_options_default": (None, [C.POINTER(SgEpipolarOptions)]),
+    "sg_slam_match_epipolar": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, C.c_int32, _ip, _dp, _u64p, _ip, _ip, _dp,
+                                         _u64p, _ip, C.POINTER(SgEpipolarOptions), _ip, _ip, _ip, _ip, _ip,
+                                         C.POINTER(SgEpipolarResult)]),
     "sg_posegraph_options_default": (None, [C.POINTER(SgPosegraphOptions)]),
     "sg_slam_optimize_pose_graph": (C.c_int, [C.c_void_p, C.POINTER(SgMap), _ip, _ip, _ip, _ip, _dp, _dp, _ip, C.c_int32,
                                               C.POINTER(SgPosegraphOptions), _ip, _dp, C.POINTER(SgSolverSummary)]),
