@@ -8,6 +8,7 @@
 #include "align_plan.h"
 #include "common.h"
 #include "dbuf.h"
+#include "device_stream.h"
 #include "hostio.h"
 
 namespace sg {
@@ -36,21 +37,18 @@ static_assert(sizeof(AlignOut) == 136, "written by k_align_select as 12 doubles 
 
 class AlignSolver {
  public:
-  explicit AlignSolver(const sg_device_options& dev, hipStream_t stream = nullptr);
-  ~AlignSolver();
+  explicit AlignSolver(const sg_device_options& dev, hipStream_t stream = nullptr) : stream_(dev, stream) {}
   // plan: PlanAlign's result for the call, made by the caller before the device is touched; num_corr: the
   // correspondences of the call (group_offset[n]).  One upload, two launches, one download.  results and corr_inlier
   // may be null.  The map is not an argument: everything the kernels read is in the plan.
   void Solve(const AlignPlan& plan, int32_t n, int32_t num_corr, const sg_align_options& o, int32_t* solved,
              sg_align_result* results, int32_t* corr_inlier);
   // Development aid (tools/align_bench.py): HIP-event time of the two launches of the calls that follow.
-  void SetTiming(bool on) { timing_ = on; }
-  double last_kernel_ms() const { return kernel_ms_; }
+  void SetTiming(bool on) { timer_.Enable(on); }
+  double last_kernel_ms() const { return timer_.last_ms(); }
 
  private:
-  sg_device_options dev_;
-  hipStream_t stream_ = nullptr;
-  bool own_stream_ = false;
+  DeviceStream stream_;
   HostIo io_;
   DBuf<AlignGroup> groups_;
   DBuf<int32_t> off_;
@@ -60,9 +58,7 @@ class AlignSolver {
   DBuf<int32_t> flags_;
   std::vector<AlignOut> out_h_;
   std::vector<int32_t> flags_h_;
-  bool timing_ = false;
-  double kernel_ms_ = 0.0;
-  hipEvent_t ev_[2] = {nullptr, nullptr};
+  KernelTimer timer_;
 };
 
 }  // namespace sg

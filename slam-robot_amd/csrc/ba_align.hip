@@ -312,25 +312,6 @@ __global__ __launch_bounds__(kAlignThreads) void k_align_select(AlignSelectArgs 
 
 }  // namespace
 
-AlignSolver::AlignSolver(const sg_device_options& dev, hipStream_t stream) : dev_(dev) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(SG_ENODEV, "no HIP device available");
-  SG_REQUIRE(dev.device >= 0 && dev.device < ndev, SG_ENODEV, "device ordinal out of range");
-  SG_HIP_CHECK(hipSetDevice(dev.device));
-  if (stream) {
-    stream_ = stream;
-  } else {
-    SG_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    own_stream_ = true;
-  }
-}
-
-AlignSolver::~AlignSolver() {
-  for (hipEvent_t e : ev_)
-    if (e) (void)hipEventDestroy(e);
-  if (own_stream_ && stream_) (void)hipStreamDestroy(stream_);
-}
-
 void AlignSolver::Solve(const AlignPlan& plan, int32_t n, int32_t num_corr, const sg_align_options& o, int32_t* solved,
                         sg_align_result* results, int32_t* corr_inlier) {
   SG_REQUIRE(solved && n > 0 && num_corr >= 0 && (int32_t)plan.groups.size() == n, SG_EINVAL, "bad argument");
@@ -345,9 +326,9 @@ void AlignSolver::Solve(const AlignPlan& plan, int32_t n, int32_t num_corr, cons
     res[i].best_hypothesis = -1;
     for (int j = 0; j < 3; ++j) res[i].best_sample[j] = -1;
   }
-  kernel_ms_ = 0.0;
+  timer_.Reset();
   if (plan.num_run > 0) {
-    SG_HIP_CHECK(hipSetDevice(dev_.device));
+    stream_.Bind();
     io_.Begin();
     io_.Up(groups_, plan.groups);
     io_.Up(off_, plan.off);
@@ -355,7 +336,7 @@ void AlignSolver::Solve(const AlignPlan& plan, int32_t n, int32_t num_corr, cons
     cand_.Resize((size_t)n * S);
     out_.Resize((size_t)n);
     flags_.Resize(std::max<size_t>(total, 1));
-    io_.FlushUp(stream_);
+    io_.FlushUp(stream_.get());
     AlignRansacArgs ra{};
     ra.groups = groups_.ptr;
     ra.off = off_.ptr;
@@ -381,26 +362,18 @@ void AlignSolver::Solve(const AlignPlan& plan, int32_t n, int32_t num_corr, cons
     sa.min_inliers = o.min_inliers;
     sa.refine = o.refine != 0;
     sa.fix_scale = ra.fix_scale;
-    if (timing_) {
-      for (hipEvent_t& e : ev_)
-        if (!e) SG_HIP_CHECK(hipEventCreate(&e));
-      SG_HIP_CHECK(hipEventRecord(ev_[0], stream_));
-    }
-    hipLaunchKernelGGL(k_align_ransac, dim3((unsigned)plan.grid), dim3(kAlignThreads), 0, stream_, ra);
+    timer_.Start(stream_.get());
+    hipLaunchKernelGGL(k_align_ransac, dim3((unsigned)plan.grid), dim3(kAlignThreads), 0, stream_.get(), ra);
     SG_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_align_select, dim3((unsigned)n), dim3(kAlignThreads), 0, stream_, sa);
+    hipLaunchKernelGGL(k_align_select, dim3((unsigned)n), dim3(kAlignThreads), 0, stream_.get(), sa);
     SG_HIP_CHECK(hipGetLastError());
-    if (timing_) SG_HIP_CHECK(hipEventRecord(ev_[1], stream_));
+    timer_.Stop(stream_.get());
     out_h_.resize((size_t)n);
     flags_h_.resize(total);
     io_.Down(out_h_.data(), out_.ptr, (size_t)n * sizeof(AlignOut));
     io_.Down(flags_h_.data(), flags_.ptr, total * sizeof(int32_t));
-    io_.FinishDown(stream_);
-    if (timing_) {
-      float ms = 0.f;
-      SG_HIP_CHECK(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
-      kernel_ms_ = ms;
-    }
+    io_.FinishDown(stream_.get());
+    timer_.Read();
     for (int i = 0; i < n; ++i) {
       if (!plan.groups[i].run) continue;   // (its result was not written)
       const AlignOut& w = out_h_[i];

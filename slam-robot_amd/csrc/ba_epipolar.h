@@ -7,6 +7,7 @@
 
 #include "common.h"
 #include "dbuf.h"
+#include "device_stream.h"
 #include "epipolar_plan.h"
 #include "hostio.h"
 
@@ -14,8 +15,7 @@ namespace sg {
 
 class EpipolarSolver {
  public:
-  explicit EpipolarSolver(const sg_device_options& dev, hipStream_t stream = nullptr);
-  ~EpipolarSolver();
+  explicit EpipolarSolver(const sg_device_options& dev, hipStream_t stream = nullptr) : stream_(dev, stream) {}
   // plan: PlanEpipolar's result for the call (plan.launch set), made by the caller before the device is touched; the
   // keypoint arrays are the call's own.  One upload, three launches, one download.  The four per-keypoint arrays [KA]
   // are all written (the empty answers for the pairs that are not live), and only after the downloaded values have
@@ -25,13 +25,11 @@ class EpipolarSolver {
            const int32_t* b_level, const sg_epipolar_options& o, int32_t* best_kp, int32_t* best_dist,
            int32_t* second_dist, int32_t* num_candidates);
   // Development aid (tools/epipolar_bench.py): HIP-event time of the three launches of the calls that follow.
-  void SetTiming(bool on) { timing_ = on; }
-  double last_kernel_ms() const { return kernel_ms_; }
+  void SetTiming(bool on) { timer_.Enable(on); }
+  double last_kernel_ms() const { return timer_.last_ms(); }
 
  private:
-  sg_device_options dev_;
-  hipStream_t stream_ = nullptr;
-  bool own_stream_ = false;
+  DeviceStream stream_;
   HostIo io_;
   DBuf<EpiPair> pairs_;
   DBuf<EpiPrepItem> prep_;
@@ -44,9 +42,7 @@ class EpipolarSolver {
   DBuf<EpiB> b_rec_;           // [KB]
   DBuf<uint4> part_;           // [plan.partials] best key, second key, candidates of one slice
   DBuf<int32_t> out_;          // [4 KA] best_kp, best_dist, second_dist, num_candidates
-  bool timing_ = false;
-  double kernel_ms_ = 0.0;
-  hipEvent_t ev_[2] = {nullptr, nullptr};
+  KernelTimer timer_;
 };
 
 }  // namespace sg

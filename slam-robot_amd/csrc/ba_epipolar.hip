@@ -13,22 +13,23 @@
 // registers; the slice goes through LDS a tile of 256 at a time, each wave scores its quarter of the tile, and in the
 // scoring loop every lane reads the same entry (a broadcast: no bank conflict), four entries a trip.  The gate comes
 // first; the depth and parallax tests and the popcounts run only for entries inside it.  best and second follow
-// hamming.hip's packed-key rule, key = (distance << 22) | b index within the pair; the four waves' answers meet in
+// best2.h's packed-key rule, key = (distance << 22) | b index within the pair; the four waves' answers meet in
 // LDS.  A tile's tail is padded with EpiPadB: an infinite nb with a NaN x_b, whose r is NaN, so the gate's comparison
 // is false and a padded entry is never counted.
 //
 // k_epi_merge: one thread per a keypoint merges its slices in slice order and sums their candidate counts.
 //
 // Every count is known on the host: no device counter, no atomic.  The keys of one a keypoint are distinct (the b
-// indices are), so the smallest and the second smallest of its keys do not depend on the order in which they are taken
-// or merged, and neither does an integer count.  A pair's records come from its own pair record and keypoints alone, so
-// its results depend neither on its position in the call nor on the run.
+// indices are), so best2.h's rule gives the same best and second whatever the order in which they are taken or
+// merged, and an integer count does not depend on it either.  A pair's records come from its own pair record and
+// keypoints alone, so its results depend neither on its position in the call nor on the run.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 
 #include "ba_epipolar.h"
+#include "best2.h"
 #include "epipolar_math.h"
 
 namespace sg {
@@ -36,8 +37,6 @@ namespace sg {
 namespace {
 
 constexpr int kEpiThreads = 256;
-constexpr unsigned kEpiKeyInf = 0xFFFFFFFFu;
-constexpr unsigned kEpiPosMask = (1u << kEpiKeyShift) - 1;
 constexpr int kEpiWaves = kEpiThreads / 64;
 constexpr int kEpiShare = kEpiTile / kEpiWaves;   // a wave's entries of a tile
 static_assert(kEpiChunk == 64 && kEpiTile == kEpiThreads, "one a keypoint per lane and one tile entry per thread");
@@ -73,17 +72,6 @@ __global__ __launch_bounds__(kEpiThreads) void k_epi_prep(EpiPrepArgs a) {
   }
 }
 
-__device__ __forceinline__ void epi_take(unsigned key, unsigned& m1, unsigned& m2) {
-  m2 = min(m2, max(m1, key));   // the median of (m1, key, m2) with m1 <= m2: the second smallest
-  m1 = min(m1, key);
-}
-
-__device__ __forceinline__ void epi_merge(unsigned& m1, unsigned& m2, unsigned o1, unsigned o2) {
-  const unsigned n2 = min(max(m1, o1), min(m2, o2));
-  m1 = min(m1, o1);
-  m2 = n2;
-}
-
 struct EpiWindowArgs {
   const EpiItem* items;
   const EpiA* a_rec;
@@ -105,8 +93,7 @@ __global__ __launch_bounds__(kEpiThreads) void k_epi_window(EpiWindowArgs a) {
   const size_t ka = (size_t)it.a0 + (live ? lane : 0);   // (an idle lane reads the chunk's first keypoint and writes nothing)
   const EpiA ra = a.a_rec[ka];
   const uint4 d0 = a.a_desc[2 * ka], d1 = a.a_desc[2 * ka + 1];
-  unsigned m1 = kEpiKeyInf, m2 = kEpiKeyInf;
-  int wn = 0;
+  unsigned m1 = kBest2Inf, m2 = kBest2Inf, wn = 0;
   for (int t0 = 0; t0 < it.bcount; t0 += kEpiTile) {
     const int tc = min(kEpiTile, it.bcount - t0);
     __syncthreads();   // the previous tile has been read
@@ -134,26 +121,17 @@ __global__ __launch_bounds__(kEpiThreads) void k_epi_window(EpiWindowArgs a) {
           const EpiB rb = srec[e + u];
           if (EpiDepth(ra, rb) && (!(a.min_parallax > 0.0) || EpiParallax(ra, rb, a.min_parallax))) {
             const uint4 q0 = sdesc[e + u][0], q1 = sdesc[e + u][1];
-            const unsigned h = __popc(q0.x ^ d0.x) + __popc(q0.y ^ d0.y) + __popc(q0.z ^ d0.z) + __popc(q0.w ^ d0.w) +
-                               __popc(q1.x ^ d1.x) + __popc(q1.y ^ d1.y) + __popc(q1.z ^ d1.z) + __popc(q1.w ^ d1.w);
-            epi_take((h << kEpiKeyShift) | (unsigned)(it.j0 + t0 + e + u), m1, m2);
+            const unsigned h = Hamming256(q0, q1, d0, d1);
+            Best2Take((h << kEpiKeyShift) | (unsigned)(it.j0 + t0 + e + u), m1, m2);
             ++wn;
           }
         }
       }
     }
   }
-  // the four waves' answers for the same 64 a keypoints meet in LDS; wave 0 merges them in wave order
-  if (wave > 0) wpart[wave - 1][lane] = make_uint4(m1, m2, (unsigned)wn, 0u);
-  __syncthreads();
-  if (wave > 0 || !live) return;
-#pragma unroll
-  for (int w = 0; w < kEpiWaves - 1; ++w) {
-    const uint4 o = wpart[w][lane];
-    epi_merge(m1, m2, o.x, o.y);
-    wn += (int)o.z;
-  }
-  a.part[(size_t)it.part0 + lane] = make_uint4(m1, m2, (unsigned)wn, 0u);
+  // the four waves' answers for the same 64 a keypoints meet in LDS
+  if (!Best2MeetWaves<kEpiWaves>(wpart, wave, lane, m1, m2, wn) || !live) return;
+  a.part[(size_t)it.part0 + lane] = make_uint4(m1, m2, wn, 0u);
 }
 
 struct EpiMergeArgs {
@@ -168,45 +146,12 @@ __global__ __launch_bounds__(kEpiChunk) void k_epi_merge(EpiMergeArgs a) {
   if ((int)threadIdx.x >= ch.count) return;
   const size_t k = (size_t)ch.a0 + threadIdx.x;
   const size_t p0 = (size_t)ch.part0 + threadIdx.x;
-  const int ns = ch.slices;
-  unsigned m1 = kEpiKeyInf, m2 = kEpiKeyInf, wn = 0;
-  for (int s0 = 0; s0 < ns; s0 += 8) {   // slice order, eight loads a trip as in k_match_merge
-    uint4 p[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) p[u] = a.part[p0 + (size_t)min(s0 + u, ns - 1) * ch.stride];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      if (s0 + u >= ns) break;
-      epi_merge(m1, m2, p[u].x, p[u].y);
-      wn += p[u].z;
-    }
-  }
-  a.out[k] = m1 == kEpiKeyInf ? -1 : (int)(m1 & kEpiPosMask);
-  a.out[(size_t)a.KA + k] = m1 == kEpiKeyInf ? -1 : (int)(m1 >> kEpiKeyShift);
-  a.out[2 * (size_t)a.KA + k] = m2 == kEpiKeyInf ? -1 : (int)(m2 >> kEpiKeyShift);
-  a.out[3 * (size_t)a.KA + k] = (int)wn;
+  unsigned m1, m2, wn;
+  Best2MergeSlices(a.part, p0, (size_t)ch.stride, ch.slices, m1, m2, wn);
+  Best2Store(a.out, (size_t)a.KA, k, Best2Decode(m1, m2, wn));
 }
 
 }  // namespace
-
-EpipolarSolver::EpipolarSolver(const sg_device_options& dev, hipStream_t stream) : dev_(dev) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(SG_ENODEV, "no HIP device available");
-  SG_REQUIRE(dev.device >= 0 && dev.device < ndev, SG_ENODEV, "device ordinal out of range");
-  SG_HIP_CHECK(hipSetDevice(dev.device));
-  if (stream) {
-    stream_ = stream;
-  } else {
-    SG_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    own_stream_ = true;
-  }
-}
-
-EpipolarSolver::~EpipolarSolver() {
-  for (hipEvent_t e : ev_)
-    if (e) (void)hipEventDestroy(e);
-  if (own_stream_ && stream_) (void)hipStreamDestroy(stream_);
-}
 
 void EpipolarSolver::Run(const EpipolarPlan& plan, const int32_t* a_offset, const double* a_xy, const uint64_t* a_desc,
                          const int32_t* a_level, const int32_t* b_offset, const double* b_xy, const uint64_t* b_desc,
@@ -223,7 +168,7 @@ void EpipolarSolver::Run(const EpipolarPlan& plan, const int32_t* a_offset, cons
                  !plan.prep.empty() && !plan.chunks.empty() && plan.prep.size() < (1u << 24) &&
                  plan.items.size() < (1u << 24) && plan.chunks.size() < (1u << 24),
              SG_EINVAL, "launch shape out of range");
-  SG_HIP_CHECK(hipSetDevice(dev_.device));
+  stream_.Bind();
   io_.Begin();
   io_.Up(pairs_, plan.pairs);
   io_.Up(prep_, plan.prep);
@@ -241,7 +186,7 @@ void EpipolarSolver::Run(const EpipolarPlan& plan, const int32_t* a_offset, cons
   b_rec_.Resize(KB);
   part_.Resize((size_t)plan.partials);
   out_.Resize(4 * KA);
-  io_.FlushUp(stream_);
+  io_.FlushUp(stream_.get());
 
   EpiPrepArgs pa{};
   pa.pairs = pairs_.ptr;
@@ -266,27 +211,18 @@ void EpipolarSolver::Run(const EpipolarPlan& plan, const int32_t* a_offset, cons
   ma.part = part_.ptr;
   ma.out = out_.ptr;
   ma.KA = (int32_t)KA;
-  if (timing_) {
-    for (hipEvent_t& e : ev_)
-      if (!e) SG_HIP_CHECK(hipEventCreate(&e));
-    SG_HIP_CHECK(hipEventRecord(ev_[0], stream_));
-  }
-  hipLaunchKernelGGL(k_epi_prep, dim3((unsigned)plan.prep.size()), dim3(kEpiThreads), 0, stream_, pa);
+  timer_.Start(stream_.get());
+  hipLaunchKernelGGL(k_epi_prep, dim3((unsigned)plan.prep.size()), dim3(kEpiThreads), 0, stream_.get(), pa);
   SG_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_epi_window, dim3((unsigned)plan.items.size()), dim3(kEpiThreads), 0, stream_, wa);
+  hipLaunchKernelGGL(k_epi_window, dim3((unsigned)plan.items.size()), dim3(kEpiThreads), 0, stream_.get(), wa);
   SG_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_epi_merge, dim3((unsigned)plan.chunks.size()), dim3(kEpiChunk), 0, stream_, ma);
+  hipLaunchKernelGGL(k_epi_merge, dim3((unsigned)plan.chunks.size()), dim3(kEpiChunk), 0, stream_.get(), ma);
   SG_HIP_CHECK(hipGetLastError());
-  if (timing_) SG_HIP_CHECK(hipEventRecord(ev_[1], stream_));
+  timer_.Stop(stream_.get());
   std::vector<int32_t> out_h(4 * KA);
   io_.Down(out_h.data(), out_.ptr, out_h.size() * sizeof(int32_t));
-  io_.FinishDown(stream_);
-  kernel_ms_ = 0.0;
-  if (timing_) {
-    float ms = 0.f;
-    SG_HIP_CHECK(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
-    kernel_ms_ = ms;
-  }
+  io_.FinishDown(stream_.get());
+  timer_.Read();
   for (int i = 0; i < n; ++i) {
     const int32_t nb = b_offset[i + 1] - b_offset[i];
     for (int32_t k = a_offset[i]; k < a_offset[i + 1]; ++k) {
@@ -296,11 +232,7 @@ void EpipolarSolver::Run(const EpipolarPlan& plan, const int32_t* a_offset, cons
         wn = 0;
         continue;
       }
-      SG_REQUIRE(wn >= 0 && wn <= nb && (wn == 0) == (bk < 0) && (wn < 2) == (sd < 0), SG_EDEVICE,
-                 "candidate count out of range");
-      SG_REQUIRE(bk < 0 ? bk == -1 && bd == -1 : bk < nb && bd >= 0 && bd <= 256, SG_EDEVICE,
-                 "best match out of range");
-      SG_REQUIRE(sd < 0 ? sd == -1 : sd >= bd && sd <= 256, SG_EDEVICE, "second distance out of range");
+      SG_REQUIRE(Best2ResultOk(bk, bd, sd, wn, nb, nb), SG_EDEVICE, "match result out of range");
     }
   }
   // outputs only after every value has been checked: a failing call writes nothing

@@ -327,10 +327,10 @@ void PoseSolver::Localize(sg_map* m, const int32_t* frames, int32_t n, const sg_
     pf.q[3] = 1.0;
     pf.t[0] = pf.t[1] = pf.t[2] = 0.0;
   }
-  kernel_ms_ = 0.0;
+  timer_.Reset();
   const size_t total = (size_t)plan_.off[n];
   if (plan_.num_run > 0) {
-    SG_HIP_CHECK(hipSetDevice(dev_.device));
+    stream_.Bind();
     io_.Begin();
     io_.Up(frames_, plan_.frames);
     io_.Up(off_, plan_.off);
@@ -342,7 +342,7 @@ void PoseSolver::Localize(sg_map* m, const int32_t* frames, int32_t n, const sg_
       loc_d_[j].Resize((size_t)n);
       flags_d_[j].Resize(std::max<size_t>(total, 1));
     }
-    io_.FlushUp(stream_);
+    io_.FlushUp(stream_.get());
     RansacArgs ra{};
     ra.frames = frames_.ptr;
     ra.off = off_.ptr;
@@ -366,14 +366,10 @@ void PoseSolver::Localize(sg_map* m, const int32_t* frames, int32_t n, const sg_
     sa.S = S;
     sa.min_inliers = lo.min_inliers;
     sa.post = 0;
-    if (timing_) {
-      for (hipEvent_t& e : ev_)
-        if (!e) SG_HIP_CHECK(hipEventCreate(&e));
-      SG_HIP_CHECK(hipEventRecord(ev_[0], stream_));
-    }
-    hipLaunchKernelGGL(k_pose_ransac, dim3((unsigned)((size_t)n * S)), dim3(kPoseThreads), 0, stream_, ra);
+    timer_.Start(stream_.get());
+    hipLaunchKernelGGL(k_pose_ransac, dim3((unsigned)((size_t)n * S)), dim3(kPoseThreads), 0, stream_.get(), ra);
     SG_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_pose_select, dim3((unsigned)n), dim3(kPoseThreads), 0, stream_, sa);
+    hipLaunchKernelGGL(k_pose_select, dim3((unsigned)n), dim3(kPoseThreads), 0, stream_.get(), sa);
     SG_HIP_CHECK(hipGetLastError());
     if (refine) {
       // the polish reads the PoseFrame array the launch above rewrote: run = 1 for exactly the SG_LOC_OK frames
@@ -381,10 +377,10 @@ void PoseSolver::Localize(sg_map* m, const int32_t* frames, int32_t n, const sg_
       sa.out = loc_d_[1].ptr;
       sa.flags = flags_d_[1].ptr;
       sa.post = 1;
-      hipLaunchKernelGGL(k_pose_select, dim3((unsigned)n), dim3(kPoseThreads), 0, stream_, sa);
+      hipLaunchKernelGGL(k_pose_select, dim3((unsigned)n), dim3(kPoseThreads), 0, stream_.get(), sa);
       SG_HIP_CHECK(hipGetLastError());
     }
-    if (timing_) SG_HIP_CHECK(hipEventRecord(ev_[1], stream_));
+    timer_.Stop(stream_.get());
     for (int j = 0; j < (refine ? 2 : 1); ++j) {
       loc_h_[j].resize((size_t)n);
       flags_h_[j].resize(total);
@@ -395,12 +391,8 @@ void PoseSolver::Localize(sg_map* m, const int32_t* frames, int32_t n, const sg_
       out_h_.resize((size_t)n);
       io_.Down(out_h_.data(), out_.ptr, (size_t)n * sizeof(PoseOut));
     }
-    io_.FinishDown(stream_);
-    if (timing_) {
-      float ms = 0.f;
-      SG_HIP_CHECK(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
-      kernel_ms_ = ms;
-    }
+    io_.FinishDown(stream_.get());
+    timer_.Read();
     for (int i = 0; i < n; ++i) {
       if (!plan_.frames[i].run) continue;   // (its result was not written)
       const LocOut& w = loc_h_[0][i];

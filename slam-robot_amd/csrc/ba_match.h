@@ -7,6 +7,7 @@
 
 #include "common.h"
 #include "dbuf.h"
+#include "device_stream.h"
 #include "hostio.h"
 #include "match_plan.h"
 
@@ -14,8 +15,7 @@ namespace sg {
 
 class MatchSolver {
  public:
-  explicit MatchSolver(const sg_device_options& dev, hipStream_t stream = nullptr);
-  ~MatchSolver();
+  explicit MatchSolver(const sg_device_options& dev, hipStream_t stream = nullptr) : stream_(dev, stream) {}
   // plan: PlanMatch's result for the call (plan.launch set), made by the caller before the device is touched; the
   // keypoints and the point list are the call's own arrays.  One upload, three launches, one download.  The four
   // per-keypoint arrays [K] and projected [n] are all written, and only after the downloaded values have been checked.
@@ -23,13 +23,11 @@ class MatchSolver {
            const uint64_t* point_desc, const sg_match_options& o, int32_t* best_point, int32_t* best_dist,
            int32_t* second_dist, int32_t* num_candidates, int32_t* projected);
   // Development aid (tools/match_bench.py): HIP-event time of the three launches of the calls that follow.
-  void SetTiming(bool on) { timing_ = on; }
-  double last_kernel_ms() const { return kernel_ms_; }
+  void SetTiming(bool on) { timer_.Enable(on); }
+  double last_kernel_ms() const { return timer_.last_ms(); }
 
  private:
-  sg_device_options dev_;
-  hipStream_t stream_ = nullptr;
-  bool own_stream_ = false;
+  DeviceStream stream_;
   HostIo io_;
   DBuf<MatchFrame> frames_;
   DBuf<MatchChunk> chunks_;
@@ -42,9 +40,7 @@ class MatchSolver {
   DBuf<int32_t> surv_pos_;     // [n * np]
   DBuf<uint4> part_;           // [slices * K] best key, second key, window size of one slice
   DBuf<int32_t> out_;          // [4 K] best_point, best_dist, second_dist, num_candidates
-  bool timing_ = false;
-  double kernel_ms_ = 0.0;
-  hipEvent_t ev_[2] = {nullptr, nullptr};
+  KernelTimer timer_;
 };
 
 }  // namespace sg

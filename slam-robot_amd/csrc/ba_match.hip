@@ -14,7 +14,7 @@
 // keeps keypoint l's pixel and descriptor in registers; the slice goes through LDS a tile of 256 at a time, each wave
 // scores its quarter of the tile, and in the scoring loop every lane reads the same entry (a broadcast: no bank
 // conflict), four entries a trip.  The fp64 distance test comes first; the popcounts run only for entries inside the
-// window.  best and second follow hamming.hip's packed-key rule, key = (distance << 22) | position; the four waves'
+// window.  best and second follow best2.h's packed-key rule, key = (distance << 22) | position; the four waves'
 // answers meet in LDS.  Splitting the survivors over the waves (not the keypoints) keeps each wave's serial walk at a
 // quarter of the slice and puts four times as many workgroups on the chip, which is what a one-frame call needs: it
 // is bound by the latency of that walk, not by throughput.  The slice count comes from np alone, so the grid is
@@ -24,16 +24,17 @@
 // k_match_merge: one thread per keypoint merges the slices that exist for its frame, in slice order, and sums their
 // window sizes.
 //
-// Order independence: the keys of one keypoint are distinct (positions are), so the smallest and the second smallest
-// of a set of keys do not depend on the order in which they are taken or merged, and neither does an integer count.
-// Every output is such a min, second-min or count over the frame's survivor set, which is itself fixed by the
-// arithmetic of Project on the inputs: the results are reproducible bit for bit although the lists are not.
+// Order independence: the keys of one keypoint are distinct (positions are), so best2.h's rule gives the same best
+// and second whatever the order of a frame's list, and an integer count does not depend on it either.  Every output
+// is such a min, second-min or count over the frame's survivor set, which is itself fixed by the arithmetic of Project
+// on the inputs: the results are reproducible bit for bit although the lists are not.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 
 #include "ba_match.h"
+#include "best2.h"
 #include "project_math.h"
 
 namespace sg {
@@ -41,8 +42,6 @@ namespace sg {
 namespace {
 
 constexpr int kMatchThreads = 256;
-constexpr unsigned kMatchKeyInf = 0xFFFFFFFFu;
-constexpr unsigned kMatchPosMask = (1u << kMatchKeyShift) - 1;
 constexpr int kMatchWaves = kMatchThreads / 64;
 constexpr int kMatchShare = kMatchTile / kMatchWaves;   // a wave's entries of a tile
 static_assert(kMatchChunk == 64 && kMatchTile == kMatchThreads, "one keypoint per lane and one tile entry per thread");
@@ -91,17 +90,6 @@ __global__ __launch_bounds__(kMatchThreads) void k_match_project(MatchProjectArg
   a.surv_pos[at] = j;
 }
 
-__device__ __forceinline__ void match_take(unsigned key, unsigned& m1, unsigned& m2) {
-  m2 = min(m2, max(m1, key));   // the median of (m1, key, m2) with m1 <= m2: the second smallest
-  m1 = min(m1, key);
-}
-
-__device__ __forceinline__ void match_merge(unsigned& m1, unsigned& m2, unsigned o1, unsigned o2) {
-  const unsigned n2 = min(max(m1, o1), min(m2, o2));
-  m1 = min(m1, o1);
-  m2 = n2;
-}
-
 struct MatchWindowArgs {
   const MatchChunk* chunks;
   const int32_t* count;       // [n] survivors per listed frame
@@ -133,8 +121,7 @@ __global__ __launch_bounds__(kMatchThreads) void k_match_window(MatchWindowArgs 
   const double2 xy = a.kp_xy[kp];
   const uint4 d0 = a.kp_desc[2 * (size_t)kp], d1 = a.kp_desc[2 * (size_t)kp + 1];
   const size_t fb = (size_t)ch.slot * a.np;
-  unsigned m1 = kMatchKeyInf, m2 = kMatchKeyInf;
-  int wn = 0;
+  unsigned m1 = kBest2Inf, m2 = kBest2Inf, wn = 0;
   for (int t0 = s0; t0 < s1; t0 += kMatchTile) {
     const int tc = min(kMatchTile, s1 - t0);
     __syncthreads();   // the previous tile has been read
@@ -165,25 +152,16 @@ __global__ __launch_bounds__(kMatchThreads) void k_match_window(MatchWindowArgs 
       for (int u = 0; u < 4; ++u) {
         if (dist2[u] <= a.r2) {   // (false for a non-finite keypoint and for the padding)
           const uint4 q0 = sdesc[e + u][0], q1 = sdesc[e + u][1];
-          const unsigned h = __popc(q0.x ^ d0.x) + __popc(q0.y ^ d0.y) + __popc(q0.z ^ d0.z) + __popc(q0.w ^ d0.w) +
-                             __popc(q1.x ^ d1.x) + __popc(q1.y ^ d1.y) + __popc(q1.z ^ d1.z) + __popc(q1.w ^ d1.w);
-          match_take((h << kMatchKeyShift) | (unsigned)spos[e + u], m1, m2);
+          const unsigned h = Hamming256(q0, q1, d0, d1);
+          Best2Take((h << kMatchKeyShift) | (unsigned)spos[e + u], m1, m2);
           ++wn;
         }
       }
     }
   }
-  // the four waves' answers for the same 64 keypoints meet in LDS; wave 0 merges them in wave order
-  if (wave > 0) wpart[wave - 1][lane] = make_uint4(m1, m2, (unsigned)wn, 0u);
-  __syncthreads();
-  if (wave > 0 || !live) return;
-#pragma unroll
-  for (int w = 0; w < kMatchWaves - 1; ++w) {
-    const uint4 o = wpart[w][lane];
-    match_merge(m1, m2, o.x, o.y);
-    wn += (int)o.z;
-  }
-  a.part[(size_t)slice * a.K + kp] = make_uint4(m1, m2, (unsigned)wn, 0u);
+  // the four waves' answers for the same 64 keypoints meet in LDS
+  if (!Best2MeetWaves<kMatchWaves>(wpart, wave, lane, m1, m2, wn) || !live) return;
+  a.part[(size_t)slice * a.K + kp] = make_uint4(m1, m2, wn, 0u);
 }
 
 struct MatchMergeArgs {
@@ -200,44 +178,14 @@ __global__ __launch_bounds__(kMatchChunk) void k_match_merge(MatchMergeArgs a) {
   if ((int)threadIdx.x >= ch.count) return;
   const int kp = ch.kp0 + threadIdx.x;
   const int ns = (a.count[ch.slot] + kMatchSlice - 1) / kMatchSlice;   // the slices k_match_window wrote
-  unsigned m1 = kMatchKeyInf, m2 = kMatchKeyInf, wn = 0;
-  for (int s0 = 0; s0 < ns; s0 += 8) {   // slice order, eight loads a trip as in k_hamming_merge
-    uint4 p[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) p[u] = a.part[(size_t)min(s0 + u, ns - 1) * a.K + kp];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      if (s0 + u >= ns) break;
-      match_merge(m1, m2, p[u].x, p[u].y);
-      wn += p[u].z;
-    }
-  }
-  a.out[kp] = m1 == kMatchKeyInf ? -1 : a.points[m1 & kMatchPosMask];
-  a.out[(size_t)a.K + kp] = m1 == kMatchKeyInf ? -1 : (int)(m1 >> kMatchKeyShift);
-  a.out[2 * (size_t)a.K + kp] = m2 == kMatchKeyInf ? -1 : (int)(m2 >> kMatchKeyShift);
-  a.out[3 * (size_t)a.K + kp] = (int)wn;
+  unsigned m1, m2, wn;
+  Best2MergeSlices(a.part, (size_t)kp, (size_t)a.K, ns, m1, m2, wn);
+  Best2Result r = Best2Decode(m1, m2, wn);
+  if (r.index >= 0) r.index = a.points[r.index];   // position in points[] -> map index
+  Best2Store(a.out, (size_t)a.K, (size_t)kp, r);
 }
 
 }  // namespace
-
-MatchSolver::MatchSolver(const sg_device_options& dev, hipStream_t stream) : dev_(dev) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(SG_ENODEV, "no HIP device available");
-  SG_REQUIRE(dev.device >= 0 && dev.device < ndev, SG_ENODEV, "device ordinal out of range");
-  SG_HIP_CHECK(hipSetDevice(dev.device));
-  if (stream) {
-    stream_ = stream;
-  } else {
-    SG_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    own_stream_ = true;
-  }
-}
-
-MatchSolver::~MatchSolver() {
-  for (hipEvent_t e : ev_)
-    if (e) (void)hipEventDestroy(e);
-  if (own_stream_ && stream_) (void)hipStreamDestroy(stream_);
-}
 
 void MatchSolver::Run(const MatchPlan& plan, const double* kp_xy, const uint64_t* kp_desc, const int32_t* points,
                       const uint64_t* point_desc, const sg_match_options& o, int32_t* best_point, int32_t* best_dist,
@@ -250,7 +198,7 @@ void MatchSolver::Run(const MatchPlan& plan, const double* kp_xy, const uint64_t
   // (n np <= 2^22 and K <= 2^20 keep both flat grids far below 2^24 workgroups)
   SG_REQUIRE(n > 0 && S > 0 && nchunk > 0 && (size_t)plan.project_blocks * n < (1u << 24) && nchunk * S < (1u << 24),
              SG_EINVAL, "launch shape out of range");
-  SG_HIP_CHECK(hipSetDevice(dev_.device));
+  stream_.Bind();
   io_.Begin();
   io_.Up(frames_, plan.frames);
   io_.Up(chunks_, plan.chunks);
@@ -267,7 +215,7 @@ void MatchSolver::Run(const MatchPlan& plan, const double* kp_xy, const uint64_t
   surv_pos_.Resize(pairs);
   part_.Resize((size_t)S * K);
   out_.Resize(4 * (size_t)K);
-  io_.FlushUp(stream_);
+  io_.FlushUp(stream_.get());
 
   MatchProjectArgs pa{};
   pa.frames = frames_.ptr;
@@ -303,39 +251,28 @@ void MatchSolver::Run(const MatchPlan& plan, const double* kp_xy, const uint64_t
   ma.points = points_.ptr;
   ma.out = out_.ptr;
   ma.K = K;
-  if (timing_) {
-    for (hipEvent_t& e : ev_)
-      if (!e) SG_HIP_CHECK(hipEventCreate(&e));
-    SG_HIP_CHECK(hipEventRecord(ev_[0], stream_));
-  }
-  hipLaunchKernelGGL(k_match_project, dim3((unsigned)(plan.project_blocks * n)), dim3(kMatchThreads), 0, stream_,
+  timer_.Start(stream_.get());
+  hipLaunchKernelGGL(k_match_project, dim3((unsigned)(plan.project_blocks * n)), dim3(kMatchThreads), 0, stream_.get(),
                      pa);
   SG_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_match_window, dim3((unsigned)(nchunk * S)), dim3(kMatchThreads), 0, stream_, wa);
+  hipLaunchKernelGGL(k_match_window, dim3((unsigned)(nchunk * S)), dim3(kMatchThreads), 0, stream_.get(), wa);
   SG_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_match_merge, dim3((unsigned)nchunk), dim3(kMatchChunk), 0, stream_, ma);
+  hipLaunchKernelGGL(k_match_merge, dim3((unsigned)nchunk), dim3(kMatchChunk), 0, stream_.get(), ma);
   SG_HIP_CHECK(hipGetLastError());
-  if (timing_) SG_HIP_CHECK(hipEventRecord(ev_[1], stream_));
+  timer_.Stop(stream_.get());
   std::vector<int32_t> out_h(4 * (size_t)K), count_h((size_t)n);
   io_.Down(out_h.data(), out_.ptr, out_h.size() * sizeof(int32_t));
   io_.Down(count_h.data(), count_.ptr, count_h.size() * sizeof(int32_t));
-  io_.FinishDown(stream_);
-  kernel_ms_ = 0.0;
-  if (timing_) {
-    float ms = 0.f;
-    SG_HIP_CHECK(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
-    kernel_ms_ = ms;
-  }
+  io_.FinishDown(stream_.get());
+  timer_.Read();
   for (int i = 0; i < n; ++i)
     SG_REQUIRE(count_h[i] >= 0 && count_h[i] <= np, SG_EDEVICE, "survivor count out of range");
   for (size_t c = 0; c < nchunk; ++c) {
     const MatchChunk& ch = plan.chunks[c];
     for (int32_t k = ch.kp0; k < ch.kp0 + ch.count; ++k) {
       const int32_t bp = out_h[k], bd = out_h[(size_t)K + k], sd = out_h[2 * (size_t)K + k], wn = out_h[3 * (size_t)K + k];
-      SG_REQUIRE(wn >= 0 && wn <= count_h[ch.slot] && (wn == 0) == (bp < 0) && (wn < 2) == (sd < 0), SG_EDEVICE,
-                 "window size out of range");
-      SG_REQUIRE(bp < 0 ? bp == -1 && bd == -1 : bd >= 0 && bd <= 256, SG_EDEVICE, "best match out of range");
-      SG_REQUIRE(sd < 0 ? sd == -1 : sd >= bd && sd <= 256, SG_EDEVICE, "second distance out of range");
+      // (bp is a map index, of which this call knows no bound)
+      SG_REQUIRE(Best2ResultOk(bp, bd, sd, wn, INT32_MAX, count_h[ch.slot]), SG_EDEVICE, "match result out of range");
     }
   }
   // outputs only after every value has been checked: a failing call writes nothing

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "dbuf.h"
+#include "device_stream.h"
 #include "hostio.h"
 #include "points_plan.h"
 
@@ -33,8 +34,7 @@ static_assert(sizeof(PointOut) == 88, "written by k_point_lm as 7 doubles and 8 
 class PointSolver {
  public:
   // stream: the HIP stream to run on (the Slam facade passes its solver's); nullptr: a stream of its own
-  explicit PointSolver(const sg_device_options& dev, hipStream_t stream = nullptr);
-  ~PointSolver();
+  explicit PointSolver(const sg_device_options& dev, hipStream_t stream = nullptr) : stream_(dev, stream) {}
   // Solves the listed points of m against the map as it is at entry; writes the locations of the solved points
   // into m, solved[n] and (if not null) summaries[n].  The summaries of every listed point are also kept in
   // summaries() until the next call.
@@ -51,22 +51,17 @@ class PointSolver {
   const std::vector<sg_triangulate_result>& triangulation_results() const { return tri_; }
   // Development aid (tools/points_bench.py, tools/triangulate_bench.py): HIP-event time of the kernel launches of
   // the calls that follow.
-  void SetTiming(bool on) { timing_ = on; }
-  double last_kernel_ms() const { return kernel_ms_; }
+  void SetTiming(bool on) { timer_.Enable(on); }
+  double last_kernel_ms() const { return timer_.last_ms(); }
 
  private:
   // The pieces Solve and Triangulate share.  Upload: plan_ to the device (out_ sized for n points).  LaunchLm:
-  // k_point_lm on the uploaded plan.  TimeBegin / TimeEnd: the HIP events around a call's launches.  Summarize:
-  // out_h_[i] into sums_[i].
+  // k_point_lm on the uploaded plan.  Summarize: out_h_[i] into sums_[i].
   void Upload(int32_t n);
   void LaunchLm(int32_t n, double range, const sg_solver_options& o);
-  void TimeBegin();
-  void TimeEnd();
   void Summarize(int32_t i);
 
-  sg_device_options dev_;
-  hipStream_t stream_ = nullptr;
-  bool own_stream_ = false;
+  DeviceStream stream_;
   HostIo io_;
   PointsPlan plan_;
   DBuf<int32_t> off_;
@@ -79,9 +74,7 @@ class PointSolver {
   std::vector<sg_solver_summary> sums_;
   DBuf<sg_triangulate_result> tri_d_;
   std::vector<sg_triangulate_result> tri_, tri_h_;
-  bool timing_ = false;
-  double kernel_ms_ = 0.0;
-  hipEvent_t ev_[2] = {nullptr, nullptr};
+  KernelTimer timer_;
 };
 
 }  // namespace sg

@@ -270,27 +270,8 @@ LmState InitialLmState(const sg_solver_options& o) {
 
 }  // namespace
 
-PointSolver::PointSolver(const sg_device_options& dev, hipStream_t stream) : dev_(dev) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(SG_ENODEV, "no HIP device available");
-  SG_REQUIRE(dev.device >= 0 && dev.device < ndev, SG_ENODEV, "device ordinal out of range");
-  SG_HIP_CHECK(hipSetDevice(dev.device));
-  if (stream) {
-    stream_ = stream;
-  } else {
-    SG_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    own_stream_ = true;
-  }
-}
-
-PointSolver::~PointSolver() {
-  for (hipEvent_t e : ev_)
-    if (e) (void)hipEventDestroy(e);
-  if (own_stream_ && stream_) (void)hipStreamDestroy(stream_);
-}
-
 void PointSolver::Upload(int32_t n) {
-  SG_HIP_CHECK(hipSetDevice(dev_.device));
+  stream_.Bind();
   io_.Begin();
   io_.Up(off_, plan_.off);
   io_.Up(obs_, plan_.obs);
@@ -298,7 +279,7 @@ void PointSolver::Upload(int32_t n) {
   io_.Up(k_, plan_.k);
   io_.Up(points_, plan_.points);
   out_.Resize((size_t)n);
-  io_.FlushUp(stream_);
+  io_.FlushUp(stream_.get());
 }
 
 void PointSolver::LaunchLm(int32_t n, double range, const sg_solver_options& o) {
@@ -317,23 +298,8 @@ void PointSolver::LaunchLm(int32_t n, double range, const sg_solver_options& o) 
       (long long)std::max(o.max_num_iterations, 0) * (std::max(o.max_num_consecutive_invalid_steps, 0) + 2) + 16;
   a.cap = (int32_t)std::min<long long>(cap, INT_MAX);
   const unsigned grid = (unsigned)((n + kPointsPerBlock - 1) / kPointsPerBlock);
-  hipLaunchKernelGGL(k_point_lm, dim3(grid), dim3(kPointThreads), 0, stream_, a, InitialLmState(o));
+  hipLaunchKernelGGL(k_point_lm, dim3(grid), dim3(kPointThreads), 0, stream_.get(), a, InitialLmState(o));
   SG_HIP_CHECK(hipGetLastError());
-}
-
-void PointSolver::TimeBegin() {
-  if (!timing_) return;
-  for (hipEvent_t& e : ev_)
-    if (!e) SG_HIP_CHECK(hipEventCreate(&e));
-  SG_HIP_CHECK(hipEventRecord(ev_[0], stream_));
-}
-
-// (after the call's download: both events have completed)
-void PointSolver::TimeEnd() {
-  if (!timing_) return;
-  float ms = 0.f;
-  SG_HIP_CHECK(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
-  kernel_ms_ = ms;
 }
 
 void PointSolver::Summarize(int32_t i) {
@@ -362,16 +328,16 @@ void PointSolver::Solve(sg_map* m, const int32_t* points, int32_t n, double rang
   none.termination_type = SG_DID_NOT_RUN;
   sums_.assign((size_t)n, none);
   for (int i = 0; i < n; ++i) solved[i] = 0;
-  kernel_ms_ = 0.0;
+  timer_.Reset();
   if (plan_.num_run > 0) {
     Upload(n);
-    TimeBegin();
+    timer_.Start(stream_.get());
     LaunchLm(n, range, o);
-    if (timing_) SG_HIP_CHECK(hipEventRecord(ev_[1], stream_));
+    timer_.Stop(stream_.get());
     out_h_.resize((size_t)n);
     io_.Down(out_h_.data(), out_.ptr, (size_t)n * sizeof(PointOut));
-    io_.FinishDown(stream_);
-    TimeEnd();
+    io_.FinishDown(stream_.get());
+    timer_.Read();
     for (int i = 0; i < n; ++i)
       if (plan_.points[i].run) Summarize(i);   // (the PointOut of a point that did not run was not written)
     // write-back only after every point's result has been checked: a failed call changes nothing

@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "dbuf.h"
+#include "device_stream.h"
 #include "hostio.h"
 #include "pose_plan.h"
 
@@ -74,8 +75,7 @@ __device__ __forceinline__ bool loc_before(const LocKey& a, const LocKey& b) {
 class PoseSolver {
  public:
   // stream: the HIP stream to run on (the Slam facade passes its solver's); nullptr: a stream of its own
-  explicit PoseSolver(const sg_device_options& dev, hipStream_t stream = nullptr);
-  ~PoseSolver();
+  explicit PoseSolver(const sg_device_options& dev, hipStream_t stream = nullptr) : stream_(dev, stream) {}
   // Solves the listed frames of m against the map as it is at entry; writes the poses of the solved frames into
   // m, solved[n] and (if not null) summaries[n].  The summaries of every listed frame are also kept in
   // summaries() until the next call.
@@ -91,8 +91,8 @@ class PoseSolver {
                 sg_solver_summary* summaries);
   // Development aid (tools/pose_bench.py, tools/localize_bench.py): HIP-event time of the k_pose_lm launch of the
   // calls that follow; after Localize, of its two to four launches.
-  void SetTiming(bool on) { timing_ = on; }
-  double last_kernel_ms() const { return kernel_ms_; }
+  void SetTiming(bool on) { timer_.Enable(on); }
+  double last_kernel_ms() const { return timer_.last_ms(); }
 
  private:
   // The pieces Solve and Localize share.  LaunchLm: k_pose_lm on the n uploaded frames (frames_, off_, records_;
@@ -100,9 +100,7 @@ class PoseSolver {
   void LaunchLm(int32_t n, double range, const sg_solver_options& o);
   void Summarize(int i);
 
-  sg_device_options dev_;
-  hipStream_t stream_ = nullptr;
-  bool own_stream_ = false;
+  DeviceStream stream_;
   HostIo io_;
   PosePlan plan_;
   DBuf<PoseFrame> frames_;
@@ -118,9 +116,7 @@ class PoseSolver {
   DBuf<int32_t> flags_d_[2];     // per record, the same two
   std::vector<LocOut> loc_h_[2];
   std::vector<int32_t> flags_h_[2];
-  bool timing_ = false;
-  double kernel_ms_ = 0.0;
-  hipEvent_t ev_[2] = {nullptr, nullptr};
+  KernelTimer timer_;
 };
 
 }  // namespace sg

@@ -308,25 +308,6 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_lm(PoseArgs a, LmState in
 
 }  // namespace
 
-PoseSolver::PoseSolver(const sg_device_options& dev, hipStream_t stream) : dev_(dev) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(SG_ENODEV, "no HIP device available");
-  SG_REQUIRE(dev.device >= 0 && dev.device < ndev, SG_ENODEV, "device ordinal out of range");
-  SG_HIP_CHECK(hipSetDevice(dev.device));
-  if (stream) {
-    stream_ = stream;
-  } else {
-    SG_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    own_stream_ = true;
-  }
-}
-
-PoseSolver::~PoseSolver() {
-  for (hipEvent_t e : ev_)
-    if (e) (void)hipEventDestroy(e);
-  if (own_stream_ && stream_) (void)hipStreamDestroy(stream_);
-}
-
 void PoseSolver::LaunchLm(int32_t n, double range, const sg_solver_options& o) {
   LmState s{};   // as BaSolver::Begin
   s.max_iter = o.max_num_iterations;
@@ -362,7 +343,7 @@ void PoseSolver::LaunchLm(int32_t n, double range, const sg_solver_options& o) {
   const long long cap =
       (long long)std::max(o.max_num_iterations, 0) * (std::max(o.max_num_consecutive_invalid_steps, 0) + 2) + 16;
   a.cap = (int32_t)std::min<long long>(cap, INT_MAX);
-  hipLaunchKernelGGL(k_pose_lm, dim3((unsigned)n), dim3(kPoseThreads), 0, stream_, a, s);
+  hipLaunchKernelGGL(k_pose_lm, dim3((unsigned)n), dim3(kPoseThreads), 0, stream_.get(), a, s);
   SG_HIP_CHECK(hipGetLastError());
 }
 
@@ -392,30 +373,22 @@ void PoseSolver::Solve(sg_map* m, const int32_t* frames, int32_t n, double range
   none.termination_type = SG_DID_NOT_RUN;
   sums_.assign((size_t)n, none);
   for (int i = 0; i < n; ++i) solved[i] = 0;
-  kernel_ms_ = 0.0;
+  timer_.Reset();
   if (plan_.num_run > 0) {
-    SG_HIP_CHECK(hipSetDevice(dev_.device));
+    stream_.Bind();
     io_.Begin();
     io_.Up(frames_, plan_.frames);
     io_.Up(off_, plan_.off);
     io_.Up(records_, plan_.records);
     out_.Resize((size_t)n);
-    io_.FlushUp(stream_);
-    if (timing_) {
-      for (hipEvent_t& e : ev_)
-        if (!e) SG_HIP_CHECK(hipEventCreate(&e));
-      SG_HIP_CHECK(hipEventRecord(ev_[0], stream_));
-    }
+    io_.FlushUp(stream_.get());
+    timer_.Start(stream_.get());
     LaunchLm(n, range, o);
-    if (timing_) SG_HIP_CHECK(hipEventRecord(ev_[1], stream_));
+    timer_.Stop(stream_.get());
     out_h_.resize((size_t)n);
     io_.Down(out_h_.data(), out_.ptr, (size_t)n * sizeof(PoseOut));
-    io_.FinishDown(stream_);
-    if (timing_) {
-      float ms = 0.f;
-      SG_HIP_CHECK(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
-      kernel_ms_ = ms;
-    }
+    io_.FinishDown(stream_.get());
+    timer_.Read();
     for (int i = 0; i < n; ++i) {
       if (!plan_.frames[i].run) continue;
       Summarize(i);

@@ -7,6 +7,7 @@
 
 #include "common.h"
 #include "dbuf.h"
+#include "device_stream.h"
 #include "hostio.h"
 #include "posegraph_plan.h"
 
@@ -20,8 +21,7 @@ constexpr int kPgWaves = kPgThreads / 64;
 class PoseGraphSolver {
  public:
   // stream: the HIP stream to run on (the Slam facade passes its solver's); nullptr: a stream of its own
-  explicit PoseGraphSolver(const sg_device_options& dev, hipStream_t stream = nullptr);
-  ~PoseGraphSolver();
+  explicit PoseGraphSolver(const sg_device_options& dev, hipStream_t stream = nullptr) : stream_(dev, stream) {}
   // Solves the plan's graphs that run (one upload, one launch, one download), then writes the map, status[n],
   // log_scale (may be null) and summaries (may be null).  The summaries of every graph are also kept in summaries()
   // until the next call.
@@ -29,13 +29,11 @@ class PoseGraphSolver {
              int32_t* status, double* log_scale, sg_solver_summary* summaries);
   const std::vector<sg_solver_summary>& summaries() const { return sums_; }
   // Development aid (tools/posegraph_bench.py): HIP-event time of the k_posegraph_lm launch of the calls that follow.
-  void SetTiming(bool on) { timing_ = on; }
-  double last_kernel_ms() const { return kernel_ms_; }
+  void SetTiming(bool on) { timer_.Enable(on); }
+  double last_kernel_ms() const { return timer_.last_ms(); }
 
  private:
-  sg_device_options dev_;
-  hipStream_t stream_ = nullptr;
-  bool own_stream_ = false;
+  DeviceStream stream_;
   HostIo io_;
   DBuf<PgGraph> graphs_;
   DBuf<int32_t> node_col_, col_node_, edge_ab_, colptr_, blk_row_, blk_col_, asm_ptr_, asm_items_, gasm_ptr_,
@@ -45,9 +43,7 @@ class PoseGraphSolver {
   std::vector<PgOut> out_h_;
   std::vector<double> x_h_;
   std::vector<sg_solver_summary> sums_;
-  bool timing_ = false;
-  double kernel_ms_ = 0.0;
-  hipEvent_t ev_[2] = {nullptr, nullptr};
+  KernelTimer timer_;
 };
 
 // sums_[g] from a graph's PgOut (shared with the CPU path of capi.cpp).

@@ -216,39 +216,20 @@ void PgSummarize(const PgOut& r, sg_solver_summary* su) {
   su->sync_timeouts = 0;   // nothing to time out on: no hand-off between workgroups
 }
 
-PoseGraphSolver::PoseGraphSolver(const sg_device_options& dev, hipStream_t stream) : dev_(dev) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(SG_ENODEV, "no HIP device available");
-  SG_REQUIRE(dev.device >= 0 && dev.device < ndev, SG_ENODEV, "device ordinal out of range");
-  SG_HIP_CHECK(hipSetDevice(dev.device));
-  if (stream) {
-    stream_ = stream;
-  } else {
-    SG_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    own_stream_ = true;
-  }
-}
-
-PoseGraphSolver::~PoseGraphSolver() {
-  for (hipEvent_t e : ev_)
-    if (e) (void)hipEventDestroy(e);
-  if (own_stream_ && stream_) (void)hipStreamDestroy(stream_);
-}
-
 void PoseGraphSolver::Solve(sg_map* m, const PgPlan& plan, const sg_posegraph_options& po, const sg_solver_options& o,
                             int32_t* status, double* log_scale, sg_solver_summary* summaries) {
   const int n = (int)plan.graphs.size();
   sg_solver_summary none{};
   none.termination_type = SG_DID_NOT_RUN;
   sums_.assign((size_t)n, none);
-  kernel_ms_ = 0.0;
+  timer_.Reset();
   std::vector<int32_t> st((size_t)n);
   for (int g = 0; g < n; ++g) st[g] = plan.graphs[g].status;
   const size_t N = plan.node_col.size(), E = plan.edge_ab.size() / 2, B = plan.blk_row.size(),
                C = plan.col_node.size();
   x_h_.assign(plan.x0.begin(), plan.x0.end());
   if (plan.num_run > 0) {
-    SG_HIP_CHECK(hipSetDevice(dev_.device));
+    stream_.Bind();
     io_.Begin();
     io_.Up(graphs_, plan.graphs);
     io_.Up(node_col_, plan.node_col);
@@ -273,7 +254,7 @@ void PoseGraphSolver::Solve(sg_map* m, const PgPlan& plan, const sg_posegraph_op
     rec1_.Resize(std::max<size_t>((size_t)kPgRec * E, 1));
     vec_.Resize(std::max<size_t>(6 * 7 * C, 1));
     out_.Resize((size_t)n);
-    io_.FlushUp(stream_);
+    io_.FlushUp(stream_.get());
 
     LmState s{};   // as BaSolver::Begin
     s.max_iter = o.max_num_iterations;
@@ -333,24 +314,16 @@ void PoseGraphSolver::Solve(sg_map* m, const PgPlan& plan, const sg_posegraph_op
     const long long cap =
         (long long)std::max(o.max_num_iterations, 0) * (std::max(o.max_num_consecutive_invalid_steps, 0) + 2) + 16;
     a.cap = (int32_t)std::min<long long>(cap, INT_MAX);
-    if (timing_) {
-      for (hipEvent_t& e : ev_)
-        if (!e) SG_HIP_CHECK(hipEventCreate(&e));
-      SG_HIP_CHECK(hipEventRecord(ev_[0], stream_));
-    }
-    hipLaunchKernelGGL(k_posegraph_lm, dim3((unsigned)n), dim3(kPgThreads), 0, stream_, a, s);
+    timer_.Start(stream_.get());
+    hipLaunchKernelGGL(k_posegraph_lm, dim3((unsigned)n), dim3(kPgThreads), 0, stream_.get(), a, s);
     SG_HIP_CHECK(hipGetLastError());
-    if (timing_) SG_HIP_CHECK(hipEventRecord(ev_[1], stream_));
+    timer_.Stop(stream_.get());
     out_h_.resize((size_t)n);
     x_h_.resize(kPgState * N);
     io_.Down(out_h_.data(), out_.ptr, (size_t)n * sizeof(PgOut));
     io_.Down(x_h_.data(), xout_.ptr, kPgState * N * sizeof(double));
-    io_.FinishDown(stream_);
-    if (timing_) {
-      float ms = 0.f;
-      SG_HIP_CHECK(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
-      kernel_ms_ = ms;
-    }
+    io_.FinishDown(stream_.get());
+    timer_.Read();
     for (int g = 0; g < n; ++g) {
       if (!plan.graphs[g].run) continue;
       PgSummarize(out_h_[g], &sums_[g]);

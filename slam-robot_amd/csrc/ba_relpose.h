@@ -7,6 +7,7 @@
 
 #include "common.h"
 #include "dbuf.h"
+#include "device_stream.h"
 #include "hostio.h"
 #include "relpose_plan.h"
 
@@ -37,20 +38,17 @@ static_assert(sizeof(RelOut) == 216, "written by k_relpose_select as 19 doubles 
 
 class RelPoseSolver {
  public:
-  explicit RelPoseSolver(const sg_device_options& dev, hipStream_t stream = nullptr);
-  ~RelPoseSolver();
+  explicit RelPoseSolver(const sg_device_options& dev, hipStream_t stream = nullptr) : stream_(dev, stream) {}
   // plan: PlanRelPoses' result for (m, pairs, n, o), made by the caller before the device is touched.  One upload,
   // two launches, one download; then the write-back of step 8.  results, rec_offset, rec_inlier, rec_obs may be null.
   void Solve(sg_map* m, const RelPlan& plan, int32_t n, const sg_relpose_options& o, int32_t* solved,
              sg_relpose_result* results, int32_t* rec_offset, int32_t* rec_inlier, int32_t* rec_obs);
   // Development aid (tools/relpose_bench.py): HIP-event time of the two launches of the calls that follow.
-  void SetTiming(bool on) { timing_ = on; }
-  double last_kernel_ms() const { return kernel_ms_; }
+  void SetTiming(bool on) { timer_.Enable(on); }
+  double last_kernel_ms() const { return timer_.last_ms(); }
 
  private:
-  sg_device_options dev_;
-  hipStream_t stream_ = nullptr;
-  bool own_stream_ = false;
+  DeviceStream stream_;
   HostIo io_;
   DBuf<RelPair> pairs_;
   DBuf<int32_t> off_;
@@ -60,9 +58,7 @@ class RelPoseSolver {
   DBuf<int32_t> flags_;
   std::vector<RelOut> out_h_;
   std::vector<int32_t> flags_h_;
-  bool timing_ = false;
-  double kernel_ms_ = 0.0;
-  hipEvent_t ev_[2] = {nullptr, nullptr};
+  KernelTimer timer_;
 };
 
 }  // namespace sg

@@ -162,7 +162,7 @@ void PointSolver::Triangulate(sg_map* m, const int32_t* points, int32_t n, const
     tri_[i].status = SG_TRI_DID_NOT_RUN;
     tri_[i].num_obs = plan_.off[i + 1] - plan_.off[i];
   }
-  kernel_ms_ = 0.0;
+  timer_.Reset();
   const bool refine = t.refine != 0;
   if (plan_.num_run > 0) {
     Upload(n);
@@ -178,21 +178,21 @@ void PointSolver::Triangulate(sg_map* m, const int32_t* points, int32_t n, const
     a.max_error_px = t.max_error_px;
     a.n = n;
     a.refine = refine;
-    TimeBegin();
+    timer_.Start(stream_.get());
     const unsigned grid = (unsigned)((n + kPointsPerBlock - 1) / kPointsPerBlock);
-    hipLaunchKernelGGL(k_point_triangulate, dim3(grid), dim3(kPointThreads), 0, stream_, a);
+    hipLaunchKernelGGL(k_point_triangulate, dim3(grid), dim3(kPointThreads), 0, stream_.get(), a);
     SG_HIP_CHECK(hipGetLastError());
     // the polish reads the PointStart array the launch above rewrote: run = 1 for exactly the SG_TRI_OK points
     if (refine) LaunchLm(n, t.range, o);
-    if (timing_) SG_HIP_CHECK(hipEventRecord(ev_[1], stream_));
+    timer_.Stop(stream_.get());
     tri_h_.resize((size_t)n);
     io_.Down(tri_h_.data(), tri_d_.ptr, (size_t)n * sizeof(sg_triangulate_result));
     if (refine) {
       out_h_.resize((size_t)n);
       io_.Down(out_h_.data(), out_.ptr, (size_t)n * sizeof(PointOut));
     }
-    io_.FinishDown(stream_);
-    TimeEnd();
+    io_.FinishDown(stream_.get());
+    timer_.Read();
     for (int i = 0; i < n; ++i) {
       if (!plan_.points[i].run) continue;   // (its result was not written)
       const sg_triangulate_result& r = tri_h_[i];

@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "best2.h"
 #include "epipolar_math.h"
 #include "slamgpu.h"
 
@@ -26,7 +27,7 @@ constexpr int kEpiTile = 256;             // b keypoints staged in LDS at a time
 constexpr int kEpiSlice = 512;            // b keypoints per workgroup of k_epi_window: a whole number of tiles
 constexpr int kEpiPrepRun = 256;          // keypoints per workgroup of k_epi_prep
 constexpr int kEpiMaxKeypoints = 1 << 20;
-constexpr int kEpiKeyShift = 22;          // the packed key: (distance << 22) | b index within the pair
+constexpr int kEpiKeyShift = kBest2Shift; // the packed key: (distance << 22) | b index within the pair (best2.h)
 constexpr int64_t kEpiMaxPartials = (int64_t)1 << 23;   // 16 bytes each: 128 MiB
 constexpr int kEpiMaxLevel = 7;
 static_assert(kEpiSlice % kEpiTile == 0, "a slice is whole tiles");

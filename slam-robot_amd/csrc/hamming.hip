@@ -13,14 +13,14 @@
 //     ds_read_b128), the next tile prefetched into registers during the current one;
 //   * each wave keeps its 64 queries' A fragments in VGPRs for the whole slice (4 row tiles x 4 K-steps);
 //   * epilogue per output: key = (2h << 22) | slice index (v_lshl_or), best = v_min, second = v_med3 — the
-//     same packed-key rule as the VALU kernel (ties -> lowest index; second = the multiset's second key);
+//     packed-key rule of best2.h (ties -> lowest index; second = the set's second key), with 2 h as the distance;
 //   * per slice: a 16-lane butterfly merges each query's keys over the tile columns, LDS merges the two
 //     train halves, one (best, index, second) triple per query and slice; k_hamming_merge combines slices
 //     in slice order.
 // The VALU popcount kernel this replaces (scalar-load train operands, 19 ops per pair) ran 70 us at
 // 10k x 10k and was bound by v_bcnt issue.
-// The expansion, the key rule and the tile (expand16, ham_take, ham_merge, ham_tile) are in hamming_tile.h, shared
-// with retrieve.hip.
+// Everything up to a slice's keys per query (expand16, ham_tile, ham_slice) is in hamming_tile.h, shared with
+// retrieve.hip: k_hamming_slices only says which run of the train set is its slice and writes the triple.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,87 +41,16 @@ __global__ __launch_bounds__(kHmThreads) void k_hamming_slices(const uint16_t* _
                                                                int3* __restrict__ part) {
   __shared__ __attribute__((aligned(16))) unsigned char tile[kHmTile * kHmPitch];
   __shared__ unsigned red[4][64][2];
-  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, g = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wq = wave & 3, wi = wave >> 2;
   const int s = blockIdx.y;
-  const int j0 = min(nt, s * slice_len), cnt = min(slice_len, nt - j0);
-  const int qbase = blockIdx.x * kHmQ + 64 * wq;
-  // A fragments: row tile rt, K-step k: query qbase + 16 rt + li, bytes 64 k + 16 g
-  v4i a[4][4];
-#pragma unroll
-  for (int rt = 0; rt < 4; ++rt) {
-    const int qi = min(qbase + 16 * rt + li, nq - 1);   // nq >= 1 (nothing is launched for nq == 0)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) a[rt][k] = expand16(qb[(size_t)qi * 16 + 4 * k + g], 0x01010101u, 0xFFFFFFFFu);
-  }
-  unsigned m1[4][4], m2[4][4];
-#pragma unroll
-  for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) m1[rt][r] = m2[rt][r] = kKeyInf;
-  const int ntile = (cnt + kHmTile - 1) / kHmTile;
-  // tile loads: 128 descriptors x 16 chunks of 16 bits, 4 chunks per thread (chunk c: descriptor c >> 4,
-  // bits 16 (c & 15) ..); descriptors past the slice end read the slice's last one (masked in the epilogue);
-  // each chunk is expanded to a 16-byte fragment (train side: set bit -> -1) on its way into LDS
-  unsigned pre[4];
-  auto load_tile = [&](int t) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = tid + kHmThreads * u;
-      const int item = min(t * kHmTile + (c >> 4), cnt - 1);
-      pre[u] = tb[(size_t)(j0 + item) * 16 + (c & 15)];
-    }
-  };
-  if (ntile > 0) load_tile(0);
-  for (int t = 0; t < ntile; ++t) {
-    __syncthreads();   // the previous tile's fragments are read
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = tid + kHmThreads * u;
-      *reinterpret_cast<v4i*>(tile + (c >> 4) * kHmPitch + 16 * (c & 15)) = expand16(pre[u], 0xFFFFFFFFu, 0x01010101u);
-    }
-    __syncthreads();
-    if (t + 1 < ntile) load_tile(t + 1);
-    if ((t + 1) * kHmTile > cnt)
-      ham_tile<true>(a, tile, wi, li, g, t * kHmTile, cnt, m1, m2);
-    else
-      ham_tile<false>(a, tile, wi, li, g, t * kHmTile, cnt, m1, m2);
-  }
-  // merge over the 16 tile columns (lanes of a 16-lane group)
-#pragma unroll
-  for (int mask = 1; mask < 16; mask <<= 1)
-#pragma unroll
-    for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const unsigned o1 = __shfl_xor(m1[rt][r], mask), o2 = __shfl_xor(m2[rt][r], mask);
-        ham_merge(m1[rt][r], m2[rt][r], o1, o2);
-      }
-  // lane li of group g takes query 16 (li >> 2) + 4 g + (li & 3) of the wave's 64
-  unsigned k1 = kKeyInf, k2 = kKeyInf;
-#pragma unroll
-  for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (li == 4 * rt + r) {
-        k1 = m1[rt][r];
-        k2 = m2[rt][r];
-      }
-  const int ql = 16 * (li >> 2) + 4 * g + (li & 3);
-  if (wi == 1) {
-    red[wq][ql][0] = k1;
-    red[wq][ql][1] = k2;
-  }
-  __syncthreads();
-  if (wi == 1) return;
-  ham_merge(k1, k2, red[wq][ql][0], red[wq][ql][1]);
-  const int q = qbase + ql;
-  if (q >= nq) return;
-  const int bd = k1 == kKeyInf ? (1 << 30) : (int)(k1 >> (kKeyShift + 1));
-  const int bi = k1 == kKeyInf ? -1 : j0 + (int)(k1 & ((1u << kKeyShift) - 1));
-  const int sd = k2 == kKeyInf ? (1 << 30) : (int)(k2 >> (kKeyShift + 1));
-  part[(size_t)s * nq + q] = make_int3(bd, bi, sd);
+  const int j0 = min(nt, s * slice_len), cnt = min(slice_len, nt - j0);   // cnt == 0 only when nt == 0
+  const HamSliceKeys r = ham_slice(qb, nq, tb, j0, cnt, blockIdx.x, tile, red);
+  if (!r.write) return;
+  const unsigned k1 = r.k1, k2 = r.k2;
+  // the key holds 2 h: one more bit to drop
+  const int bd = k1 == kBest2Inf ? (1 << 30) : (int)(k1 >> (kKeyShift + 1));
+  const int bi = k1 == kBest2Inf ? -1 : j0 + (int)(k1 & kBest2IndexMask);
+  const int sd = k2 == kBest2Inf ? (1 << 30) : (int)(k2 >> (kKeyShift + 1));
+  part[(size_t)s * nq + r.q] = make_int3(bd, bi, sd);
 }
 
 __global__ void k_hamming_merge(const int3* __restrict__ part, int nq, int nslice, int nt, int32_t* best_idx,

@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "dbuf.h"
+#include "device_stream.h"
 #include "hostio.h"
 
 namespace sg {
@@ -14,8 +15,7 @@ class MapOps {
  public:
   // stream: the HIP stream to run on (the Slam facade passes its solver's, so the object uses one hardware
   // queue); nullptr: a stream of its own
-  explicit MapOps(const sg_device_options& dev, hipStream_t stream = nullptr);
-  ~MapOps();
+  explicit MapOps(const sg_device_options& dev, hipStream_t stream = nullptr) : stream_(dev, stream) {}
   // LocalMap::Clean (localmap.cpp:283-398): returns the reference's bool (0 when observations were disabled).
   int Clean(sg_map* m, double error_threshold);
   // LocalMap::ApplyEpipolarConstraint (localmap.cpp:232-276): returns the number of points over the cut.
@@ -27,9 +27,7 @@ class MapOps {
  private:
   void Upload(const sg_map* m);
   void Download(sg_map* m, bool X, bool unc);
-  sg_device_options dev_;
-  hipStream_t stream_ = nullptr;
-  bool own_stream_ = false;
+  DeviceStream stream_;
   HostIo io_;   // uploads / downloads without a copy engine (hostio.h)
   int P_ = 0, M_ = 0;
   int32_t counters_h_[2] = {1, 0};

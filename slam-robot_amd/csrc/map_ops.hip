@@ -352,23 +352,6 @@ __global__ __launch_bounds__(kThreads) void k_normalize(NormArgs a, double* q, d
 
 }  // namespace
 
-MapOps::MapOps(const sg_device_options& dev, hipStream_t stream) : dev_(dev) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(SG_ENODEV, "no HIP device available");
-  SG_REQUIRE(dev.device >= 0 && dev.device < ndev, SG_ENODEV, "device ordinal out of range");
-  SG_HIP_CHECK(hipSetDevice(dev.device));
-  if (stream) {
-    stream_ = stream;
-  } else {
-    SG_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    own_stream_ = true;
-  }
-}
-
-MapOps::~MapOps() {
-  if (own_stream_ && stream_) (void)hipStreamDestroy(stream_);
-}
-
 // Upload a LocalMap and list each point's observations in TrackedPoint::observations() order (two stable
 // counting sorts: by frame, then by point).
 void MapOps::Upload(const sg_map* m) {
@@ -393,8 +376,8 @@ void MapOps::Upload(const sg_map* m) {
     std::vector<int32_t> fill(poff.begin(), poff.end() - 1);
     for (int i = 0; i < M; ++i) pobs[fill[m->obs_point[byf[i]]]++] = byf[i];
   }
-  hipStream_t s = stream_;
-  SG_HIP_CHECK(hipSetDevice(dev_.device));
+  hipStream_t s = stream_.get();
+  stream_.Bind();
   io_.Begin();
   io_.Up(k_, m->k, 7 * (size_t)m->num_cameras);
   io_.Up(q_, m->q, 4 * (size_t)F);
@@ -424,7 +407,7 @@ void MapOps::Download(sg_map* m, bool X, bool unc) {
   io_.Down(m->point_flags, flags_.ptr, 4 * (size_t)P_);
   io_.Down(m->obs_disabled, obs_dis_.ptr, 4 * (size_t)M_);
   io_.Down(counters_h_, counters_.ptr, 8);
-  io_.FinishDown(stream_);
+  io_.FinishDown(stream_.get());
 }
 
 static MapDev MakeMapDev(DBuf<double>& k, DBuf<double>& q, DBuf<double>& t, DBuf<int32_t>& fcam, DBuf<double>& X,
@@ -460,8 +443,8 @@ int MapOps::Clean(sg_map* m, double error_threshold) {
                               pobs_, cand_, changed_, scal_, counters_, P_);
   if (P_ > 0) {
     const int nb = (P_ + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL(k_clean_walk, dim3(nb), dim3(kThreads), 0, stream_, d, error_threshold);
-    hipLaunchKernelGGL(k_clean_cut, dim3(nb), dim3(kThreads), 0, stream_, d, error_threshold);
+    hipLaunchKernelGGL(k_clean_walk, dim3(nb), dim3(kThreads), 0, stream_.get(), d, error_threshold);
+    hipLaunchKernelGGL(k_clean_cut, dim3(nb), dim3(kThreads), 0, stream_.get(), d, error_threshold);
     SG_HIP_CHECK(hipGetLastError());
   }
   Download(m, true, true);
@@ -472,8 +455,8 @@ void MapOps::Normalize(sg_map* m) {
   SG_REQUIRE(m && m->num_frames >= 0 && m->num_points >= 0, SG_EINVAL, "bad map");
   if (m->num_frames < 2) return;   // localmap.cpp:115-116
   const int F = m->num_frames, P = m->num_points;
-  hipStream_t s = stream_;
-  SG_HIP_CHECK(hipSetDevice(dev_.device));
+  hipStream_t s = stream_.get();
+  stream_.Bind();
   io_.Begin();
   io_.Up(q_, m->q, 4 * (size_t)F);
   io_.Up(t_, m->t, 3 * (size_t)F);
@@ -496,7 +479,7 @@ int MapOps::ApplyEpipolarConstraint(sg_map* m) {
   const MapDev d = MakeMapDev(k_, q_, t_, fcam_, X_, flags_, unc_, obs_pt_, obs_err_, obs_frame_, obs_dis_, poff_,
                               pobs_, cand_, changed_, scal_, counters_, P_);
   if (P_ > 0) {
-    hipLaunchKernelGGL(k_epipolar, dim3((P_ + kThreads - 1) / kThreads), dim3(kThreads), 0, stream_, d);
+    hipLaunchKernelGGL(k_epipolar, dim3((P_ + kThreads - 1) / kThreads), dim3(kThreads), 0, stream_.get(), d);
     SG_HIP_CHECK(hipGetLastError());
   }
   Download(m, false, false);

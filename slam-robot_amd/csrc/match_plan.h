@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "best2.h"
 #include "slamgpu.h"
 
 namespace sg {
@@ -21,7 +22,7 @@ constexpr int kMatchChunk = 64;            // keypoints per workgroup of k_match
 constexpr int kMatchTile = 256;            // survivors staged in LDS at a time (one per thread, a quarter per wave)
 constexpr int kMatchSlice = 512;           // survivors per workgroup of k_match_window: a whole number of tiles
 constexpr int kMatchMaxKeypoints = 1 << 20;
-constexpr int kMatchKeyShift = 22;         // the packed key: (distance << 22) | position, hamming.hip's kKeyShift
+constexpr int kMatchKeyShift = kBest2Shift;   // the packed key: (distance << 22) | position (best2.h)
 constexpr int64_t kMatchMaxPairs = (int64_t)1 << kMatchKeyShift;   // n * np
 static_assert(kMatchSlice % kMatchTile == 0, "a slice is whole tiles");
 

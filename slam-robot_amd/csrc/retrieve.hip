@@ -1,10 +1,10 @@
 // retrieve.hip — keyframe retrieval: one frame's descriptors against every keyframe of a device-resident database in
 // one call (sg_matcher_db_*, include/slamgpu.h).  Three launches serve the whole database:
-//   k_retrieve_slices       hamming.hip's matrix-core distance tiles and packed-key arg-min (hamming_tile.h), with the
-//                           train side segmented: blockIdx.y walks the host-planned work list of (set, first, count)
-//                           slices (retrieve_plan.h), blockIdx.x the groups of 256 queries.  The slice-local index goes
-//                           into the key; the partial written per (item, query) is the pair of packed keys rebased to
-//                           the index within the set, so a smaller key is a smaller (distance, index in the set).
+//   k_retrieve_slices       hamming.hip's slice body (ham_slice, hamming_tile.h) with the train side segmented:
+//                           blockIdx.y walks the host-planned work list of (set, first, count) slices
+//                           (retrieve_plan.h), blockIdx.x the groups of 256 queries.  The partial written per (item,
+//                           query) is the slice's pair of packed keys rebased to the index within the set, so a
+//                           smaller key is a smaller (distance, index in the set).
 //   k_retrieve_merge_claim  per (set, query): the set's slices combined in slice order (best = min key, second = the
 //                           multiset's second key), the acceptance rule, and one 32-bit atomicMin of
 //                           (best_dist << 22) | query on the claim slot of the best descriptor.  Keys are distinct, so
@@ -29,96 +29,24 @@ namespace sg {
 namespace {
 
 static_assert(kRetrieveQ == kHmQ && kRetrieveTile == kHmTile, "the planner's shapes are the kernel's");
-constexpr unsigned kIdxMask = (1u << kKeyShift) - 1;
 
-// The slice kernel: k_hamming_slices with the slice taken from the work list.  it = (set, first, count, base).
+// The slice kernel: the slice comes from the work list, it = (set, first, count, base).
 __global__ __launch_bounds__(kHmThreads) void k_retrieve_slices(const uint16_t* __restrict__ qb, int nq,
                                                                 const uint16_t* __restrict__ tb,
                                                                 const int4* __restrict__ items,
                                                                 uint2* __restrict__ part) {
   __shared__ __attribute__((aligned(16))) unsigned char tile[kHmTile * kHmPitch];
   __shared__ unsigned red[4][64][2];
-  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, g = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wq = wave & 3, wi = wave >> 2;
   const int4 it = items[blockIdx.y];
-  const int first = __builtin_amdgcn_readfirstlane(it.y), cnt = __builtin_amdgcn_readfirstlane(it.z);
+  const int first = __builtin_amdgcn_readfirstlane(it.y), cnt = __builtin_amdgcn_readfirstlane(it.z);   // cnt >= 1
   const int j0 = __builtin_amdgcn_readfirstlane(it.w);
-  const int qbase = blockIdx.x * kHmQ + 64 * wq;
-  // A fragments: row tile rt, K-step k: query qbase + 16 rt + li, bytes 64 k + 16 g
-  v4i a[4][4];
-#pragma unroll
-  for (int rt = 0; rt < 4; ++rt) {
-    const int qi = min(qbase + 16 * rt + li, nq - 1);   // nq >= 1 (nothing is launched for nq == 0)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) a[rt][k] = expand16(qb[(size_t)qi * 16 + 4 * k + g], 0x01010101u, 0xFFFFFFFFu);
-  }
-  unsigned m1[4][4], m2[4][4];
-#pragma unroll
-  for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) m1[rt][r] = m2[rt][r] = kKeyInf;
-  const int ntile = (cnt + kHmTile - 1) / kHmTile;   // cnt >= 1: an empty set has no work item
-  // tile loads as in k_hamming_slices: descriptors past the slice end read the slice's last one (masked in the
-  // epilogue), so no load leaves the set
-  unsigned pre[4];
-  auto load_tile = [&](int t) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = tid + kHmThreads * u;
-      const int item = min(t * kHmTile + (c >> 4), cnt - 1);
-      pre[u] = tb[(size_t)(j0 + item) * 16 + (c & 15)];
-    }
-  };
-  load_tile(0);
-  for (int t = 0; t < ntile; ++t) {
-    __syncthreads();   // the previous tile's fragments are read
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = tid + kHmThreads * u;
-      *reinterpret_cast<v4i*>(tile + (c >> 4) * kHmPitch + 16 * (c & 15)) = expand16(pre[u], 0xFFFFFFFFu, 0x01010101u);
-    }
-    __syncthreads();
-    if (t + 1 < ntile) load_tile(t + 1);
-    if ((t + 1) * kHmTile > cnt)
-      ham_tile<true>(a, tile, wi, li, g, t * kHmTile, cnt, m1, m2);
-    else
-      ham_tile<false>(a, tile, wi, li, g, t * kHmTile, cnt, m1, m2);
-  }
-  // merge over the 16 tile columns (lanes of a 16-lane group)
-#pragma unroll
-  for (int mask = 1; mask < 16; mask <<= 1)
-#pragma unroll
-    for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const unsigned o1 = __shfl_xor(m1[rt][r], mask), o2 = __shfl_xor(m2[rt][r], mask);
-        ham_merge(m1[rt][r], m2[rt][r], o1, o2);
-      }
-  // lane li of group g takes query 16 (li >> 2) + 4 g + (li & 3) of the wave's 64
-  unsigned k1 = kKeyInf, k2 = kKeyInf;
-#pragma unroll
-  for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (li == 4 * rt + r) {
-        k1 = m1[rt][r];
-        k2 = m2[rt][r];
-      }
-  const int ql = 16 * (li >> 2) + 4 * g + (li & 3);
-  if (wi == 1) {
-    red[wq][ql][0] = k1;
-    red[wq][ql][1] = k2;
-  }
-  __syncthreads();
-  if (wi == 1) return;
-  ham_merge(k1, k2, red[wq][ql][0], red[wq][ql][1]);
-  const int q = qbase + ql;
-  if (q >= nq) return;
+  const HamSliceKeys r = ham_slice(qb, nq, tb, j0, cnt, blockIdx.x, tile, red);
+  if (!r.write) return;
   // slice index -> index within the set (first + index < 2^16: no carry into the distance bits)
-  if (k1 != kKeyInf) k1 += (unsigned)first;
-  if (k2 != kKeyInf) k2 += (unsigned)first;
-  part[(size_t)blockIdx.y * nq + q] = make_uint2(k1, k2);
+  unsigned k1 = r.k1, k2 = r.k2;
+  if (k1 != kBest2Inf) k1 += (unsigned)first;
+  if (k2 != kBest2Inf) k2 += (unsigned)first;
+  part[(size_t)blockIdx.y * nq + r.q] = make_uint2(k1, k2);
 }
 
 // sets[s] = (item0, nitems, offset, n).  cell[s nq + i] = (best index within the set, best distance) of a candidate,
@@ -132,14 +60,14 @@ __global__ __launch_bounds__(kRetrieveQ) void k_retrieve_merge_claim(const uint2
   const int4 rec = sets[s];
   const int i = blockIdx.x * kRetrieveQ + threadIdx.x;
   if (rec.y == 0 || i >= nq) return;
-  unsigned m1 = kKeyInf, m2 = kKeyInf;
+  unsigned m1 = kBest2Inf, m2 = kBest2Inf;
   for (int u = 0; u < rec.y; ++u) {   // slice order = index order within the set
     const uint2 p = part[(size_t)(rec.x + u) * nq + i];
-    ham_merge(m1, m2, p.x, p.y);
+    Best2Merge(m1, m2, p.x, p.y);
   }
   // n >= 1, so m1 is a key: (2 h << 22) | index; m2 is one only with n >= 2
-  const int bd = (int)(m1 >> (kKeyShift + 1)), bi = (int)(m1 & kIdxMask);
-  const int sd = m2 == kKeyInf ? -1 : (int)(m2 >> (kKeyShift + 1));
+  const int bd = (int)(m1 >> (kKeyShift + 1)), bi = (int)(m1 & kBest2IndexMask);
+  const int sd = m2 == kBest2Inf ? -1 : (int)(m2 >> (kKeyShift + 1));
   const bool ok = bd <= max_dist && (sd < 0 || 100 * bd <= ratio_percent * sd);
   cell[(size_t)s * nq + i] = ok ? make_int2(bi, bd) : make_int2(-1, -1);
   if (ok) atomicMin(&claim[rec.z + bi], ((unsigned)bd << kRetrieveClaimShift) | (unsigned)i);
